@@ -6,11 +6,17 @@ eos suppressed: random-init weights never emit a natural eos pattern) -> detoken
 BASELINE.json configs[1] (single shape pc_examples/mouse.npy, 350M shape, bf16, greedy, KV-cache decode); at N>1 every
 rank runs the same per-GPU work on its own shape (weak scaling, weights broadcast once over RCCL, no per-step collective).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `value` = face-tokens/s over all ranks (generated tokens incl. the dropped first and the
-last slot) with the input cloud already resident in HBM.
+last slot) with the input cloud already resident in HBM; `ms_per_step` = wall milliseconds of one timed step.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the benchmark measures
+and checks: per-phase times, the decode-step roofline, measured HBM / GEMM peaks, the CPU baseline, the batch 8 / 64 tables,
+the fp32 and fp16 policies, the encoder error against tests/golden/full.npz.
+`--dump-outputs DIR` writes what the last timed step returned (coords, tokens, lengths, ids, latents of every shape) as
+DIR/<name>.npy: float32 for float arrays, float64 for integer ones; inputs are seeded, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -28,8 +34,9 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 from meshanything_amd.config import MAConfig, DTYPE_BF16, DTYPE_F16, DTYPE_F32  # noqa: E402
-from meshanything_amd.checkpoint import synthetic_state_dict          # noqa: E402
+from meshanything_amd.checkpoint import synthetic_items, synthetic_state_dict          # noqa: E402
 
+DUMP_CAP_BYTES = 60 << 20  # --dump-outputs writes at most this much array data
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s measured achievable
 # health counters of the fused decode launches (ma_engine_get_option): generations that fell back to the launch chain, sweeps that gave up, the error word of
 # the last fall-back, scalar sweeps a vector look had to finish (rows_attn.hpp), long-lived blocks
@@ -48,6 +55,22 @@ def normalize_pc(pc_normal: np.ndarray) -> np.ndarray:
     """Dataset.__getitem__ normalisation (main.py:45-58) -- product-side copy lives in meshanything_amd/data.py."""
     from meshanything_amd.data import normalize_pc as f
     return f(pc_normal)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """arrays (name -> ndarray) as path/<name>.npy: float arrays as float32, integer ones as float64 (exact).  When they
+    exceed DUMP_CAP_BYTES together, every array above an even share of the cap is replaced by a sample of its flattened
+    elements drawn with a fixed seed (the same indices for the same shapes, run after run)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: v.astype(np.float32 if np.issubdtype(v.dtype, np.floating) else np.float64) for k, v in arrays.items()}
+    if sum(v.nbytes for v in conv.values()) > DUMP_CAP_BYTES:
+        share = DUMP_CAP_BYTES // len(conv)
+        for k, v in conv.items():
+            if v.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+                conv[k] = v.reshape(-1)[idx]
+    for k, v in conv.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def gemv_bytes_per_step(cfg: MAConfig, esz: int):
@@ -235,8 +258,13 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="shapes per GPU decoded together; default: 1 at --gpus 1 (BASELINE.json configs[1]), "
                                                          "8 at --gpus N > 1 (the metric's 'batch=8xN shapes'); configs 3 / 5 use 64 / 8")
     ap.add_argument("--sampling", action="store_true", help="top-k 50 / top-p 0.95 sampling (configs 3-4) instead of greedy")
-    ap.add_argument("--no-batched-table", action="store_true", help="skip the batch 8 / 64 decode-step table of the default run")
+    ap.add_argument("--no-batched-table", action="store_true", help="skip the batch 8 / 64 decode-step table of a --full run")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beyond the headline figure "
+                                                        "(phases, roofline, peaks, CPU baseline, batched tables, other precisions, encoder error)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -268,6 +296,8 @@ def main():
     def items():                                            # only called on rank 0
         # random-init weights in the reference key layout (no network).  init="diverse": the default init's greedy stream is ONE token
         # for ever (checkpoint.py); this one depends on its own tokens and positions -- `tokens_distinct` in the JSON line shows it
+        if not args.full:                                   # a plain run needs them once: streamed tensor by tensor, nothing kept
+            return synthetic_items(cfg, init="diverse")
         sd.update(synthetic_state_dict(cfg, init="diverse"))
         return sd.items()
     # weights travel once, rank 0 -> all, as ONE RCCL broadcast of the packed arena over xGMI
@@ -310,15 +340,22 @@ def main():
     # health of the fused decode launches over everything this engine ran so far (a generation that lost them was re-run on the
     # five-launch chain: correct, slower, and visible here)
     health = {k: eng.get_option(k) for k in HEALTH_KEYS}
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step, every rank's shapes in global shape order
+        mine = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()}
+        per_rank = dp.gather_to_rank0(mine, rank, world) if use_dist else [mine]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: np.concatenate([r[k] for r in per_rank]) for k in mine})
     # encoder activations of shape 0 (mouse.npy) against the reference's own perceiver (tests/golden/full.npz; the encoder weights of
     # init="diverse" are the default ones): the north star's 1e-5
     enc_err = None
-    if rank == 0 and pl["shapes"][0] == 0:
+    if args.full and rank == 0 and pl["shapes"][0] == 0:
         gold = np.load(os.path.join(REPO, "tests", "golden", "full.npz"))
         lat0 = out["latents"][0].cpu().numpy()
         enc_err = float(max(np.abs(lat0[gold["full_rows"]] - gold["full_latents_rows"]).max(), np.abs(lat0[:, :8] - gold["full_latents_cols8"]).max()))
 
-    if rank == 0:
+    full = {}
+    if rank == 0 and args.full:
         esz = 4 if args.dtype == "fp32" else 2
         # ---- per-phase times (one extra pass, HIP events on the current stream) ----
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
@@ -474,6 +511,10 @@ def main():
                            "tokens_equal_to_the_bf16_run": int((oh["tokens"][0].cpu() == out["tokens"][0].cpu()).sum()),
                            "note": "MA_DTYPE_F16 policy (the reference's fp16-autocast precision class), same cloud and weights, one warm mesh"}
             eng_h.close()
+        full = {"batched_decode_steps": batched, "batch8_generation": batch8_generation, "dense_phases": dense, "phases_ms": {k: round(v, 3) for k, v in phases.items()},
+                "fp32_exact": fp32_exact, "fp16_policy": fp16_policy, "roofline": roofline, "cpu_baseline": cpu,
+                "encoder_max_abs_err": enc_err, "measured_peaks": peaks, "fused_launch_health": {"timed_region": health, "after_profiling": health_after}}
+    if rank == 0:
         total_tokens = world * args.steps * tokens_per_step
         res = {
             "metric": f"face-tokens/sec ({args.faces}-face cap, batch {args.batch} per GPU) + sec/mesh", "value": round(total_tokens / dt, 2), "unit": "face-tokens/s",
@@ -482,11 +523,10 @@ def main():
             "config": {"workload": pl["workload"],
                        "global_batch": pl["global_batch"], "tokens_per_mesh": cfg.max_new_tokens, "parallelism": pl["parallelism"],
                        "weights": "seeded random init in the reference key layout (no checkpoint available offline), init=diverse: checkpoint.py"},
-            "sec_per_mesh": round(dt / args.steps / args.batch, 4), "batched_decode_steps": batched, "batch8_generation": batch8_generation, "dense_phases": dense, "phases_ms": {k: round(v, 3) for k, v in phases.items()},
-            "weights_load_s": round(t_load, 2), "fp32_exact": fp32_exact, "fp16_policy": fp16_policy, "roofline": roofline, "cpu_baseline": cpu,
-            "tokens_distinct": tokens_distinct, "encoder_max_abs_err": enc_err, "fused_launch_health": {"timed_region": health, "after_profiling": health_after},
-            "measured_peaks": peaks,
+            "sec_per_mesh": round(dt / args.steps / args.batch, 4), "weights_load_s": round(t_load, 2), "tokens_distinct": tokens_distinct,
+            "fused_launch_health": {"timed_region": health},
         }
+        res.update(full)
         if real_stdout is not None:
             os.write(real_stdout, (json.dumps(res) + "\n").encode())
         else:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6, GPU box: the stages named in $STAGES (space separated) on the tree as it stands; everything lands in gpurun_out/$TAG/
 #   suite   pytest -m gpu + smoke            dense   scripts/prof_dense.py (dense-phase times per batch) + its rocprof kernel stats at B = $PB
-#   calib   scripts/calib_library_gemm.py    bench   bench.py (defaults)         b8 / cfg5   bench.py --batch 8 [--faces 1600]
+#   calib   scripts/calib_library_gemm.py    bench   bench.py --full             b8 / cfg5   bench.py --full --batch 8 [--faces 1600]
 #   exp     the MA_EXPERIMENTAL tests        trace8  the 8-row step's timeline
 #   gemmtests  the dense GEMM kernel tests (-s: their timing lines)    stress  scripts/stress_gemm256.py
 #   fp32    the fp32 policy on the fused launches (bitwise tests, gates, one mesh each way)      cfg3    bench.py --batch 64 --sampling
@@ -36,11 +36,11 @@ for st in $STAGES; do
     calib)
       timeout 600 python scripts/calib_library_gemm.py 2>&1 | grep -v amdgpu.ids > $O/calib_library_gemm.txt; cat $O/calib_library_gemm.txt ;;
     bench)
-      timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo ;;
+      timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo ;;
     b8)
-      timeout 600 python bench.py --batch 8 --steps 2 --warmup 1 --no-cpu-baseline > $O/b8_800.json 2> $O/b8.err; cut -c1-400 $O/b8_800.json; echo ;;
+      timeout 600 python bench.py --full --batch 8 --steps 2 --warmup 1 --no-cpu-baseline > $O/b8_800.json 2> $O/b8.err; cut -c1-400 $O/b8_800.json; echo ;;
     cfg5)
-      timeout 600 python bench.py --batch 8 --faces 1600 --steps 1 --warmup 0 --no-cpu-baseline > $O/cfg5_b8_1600.json 2> $O/cfg5.err; cut -c1-400 $O/cfg5_b8_1600.json; echo ;;
+      timeout 600 python bench.py --full --batch 8 --faces 1600 --steps 1 --warmup 0 --no-cpu-baseline > $O/cfg5_b8_1600.json 2> $O/cfg5.err; cut -c1-400 $O/cfg5_b8_1600.json; echo ;;
     trace8)
       timeout 300 python scripts/trace_step.py --batch 8 --lens 300,3858,7300 --dist 2>&1 | grep -v amdgpu.ids > $O/trace_b8.txt; grep -E "len|attn |fc1 " $O/trace_b8.txt ;;
     gemmtests)
@@ -80,14 +80,14 @@ PY
     benchprof)
       # the kernel trace of the bench command itself (roofline.avg_launch_us must agree with it) and of the 8-row workload
       cd /tmp; rm -rf /tmp/prof_b /tmp/prof_b8
-      timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_b -o b --output-format csv -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batched-table > $O/bench_profiled.json 2> $O/bench_profiled.err
+      timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_b -o b --output-format csv -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-batched-table > $O/bench_profiled.json 2> $O/bench_profiled.err
       for f in $(find /tmp/prof_b -name "*kernel_stats*.csv"); do cp $f $O/bench_kernel_stats.csv; done
       head -6 $O/bench_kernel_stats.csv | cut -c1-200
-      timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_b8 -o b --output-format csv -- python $R/bench.py --batch 8 --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_b8_profiled.json 2> $O/bench_b8_profiled.err
+      timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_b8 -o b --output-format csv -- python $R/bench.py --full --batch 8 --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_b8_profiled.json 2> $O/bench_b8_profiled.err
       for f in $(find /tmp/prof_b8 -name "*kernel_stats*.csv"); do cp $f $O/bench_batch8_kernel_stats.csv; done
       head -5 $O/bench_batch8_kernel_stats.csv | cut -c1-200; cd $R ;;
     cfg3)
-      timeout 900 python bench.py --batch 64 --sampling --steps 1 --warmup 0 --no-cpu-baseline > $O/cfg3_b64_sampling.json 2> $O/cfg3.err; cut -c1-400 $O/cfg3_b64_sampling.json; echo ;;
+      timeout 900 python bench.py --full --batch 64 --sampling --steps 1 --warmup 0 --no-cpu-baseline > $O/cfg3_b64_sampling.json 2> $O/cfg3.err; cut -c1-400 $O/cfg3_b64_sampling.json; echo ;;
     *) echo "unknown stage $st" ;;
   esac
 done

@@ -67,3 +67,25 @@ def test_config_4_is_512_shapes_each_once_with_its_own_uniform_stream():
     assert len(streams) == 512, "two rows of the job would draw from the same uniform stream"
     # the greedy 8 x N default keeps the same seed plumbing
     assert len({b.plan(gpus=4, batch=0, rank=r, world=4)["seed"] for r in range(4)}) == 4
+
+
+def test_dump_outputs_are_float_and_capped(tmp_path):
+    """`--dump-outputs DIR`: float arrays as float32, integer ones as float64 (exact), nothing else; past the cap every large array
+    becomes a sample drawn with a fixed seed, the same one run after run."""
+    import numpy as np
+    b = _bench()
+    small = {"coords": np.full((1, 4, 3, 3), np.nan, np.float32), "tokens": np.arange(2 ** 40, 2 ** 40 + 7, dtype=np.int64)[None],
+             "lengths": np.array([7], np.int32)}
+    b.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["coords.npy", "lengths.npy", "tokens.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "s" / f"{k}.npy")
+        assert got.dtype == (np.float32 if k == "coords" else np.float64) and got.shape == v.shape
+        assert np.array_equal(got, v, equal_nan=True)
+    big = dict(small, latents=np.random.default_rng(1).random((b.DUMP_CAP_BYTES // 4 + 1,), dtype=np.float32))
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), big)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= b.DUMP_CAP_BYTES + 4096
+    la, lb = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "b" / "latents.npy")
+    assert la.size < big["latents"].size and np.array_equal(la, lb) and np.isin(la, big["latents"]).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "tokens.npy"), small["tokens"])
