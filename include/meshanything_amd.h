@@ -35,7 +35,8 @@ enum {
     MA_ERR_UNKNOWN_TENSOR = -4, /* ma_engine_load_weights: key not part of the checkpoint layout */
     MA_ERR_SHAPE = -5,          /* tensor shape/dtype does not match the layout */
     MA_ERR_MISSING = -6,        /* ma_engine_finalize_weights: required tensors were never loaded */
-    MA_ERR_NCCL = -7            /* RCCL call failed / librccl not loadable */
+    MA_ERR_NCCL = -7,           /* RCCL call failed / librccl not loadable */
+    MA_ERR_CAPACITY = -8        /* an output buffer is smaller than the result (the result's size is still reported) */
 };
 
 /* element types: engine policy (ma_config.dtype) and source-tensor dtypes of ma_tensor_desc */
@@ -305,6 +306,33 @@ MA_API int  ma_engine_persist_available(ma_engine *e);
 MA_API int  ma_persist_trace(ma_engine *e, int kv_len, uint64_t *host_out, int32_t *n_events, void *stream);
 /* copies the logits of the most recent decode step of batch row `row` (codebook_size + 3 floats) into a device buffer */
 MA_API int  ma_engine_read_logits(ma_engine *e, int row, float *out, void *stream);
+
+/* ---- watertight remeshing of a mesh input (csrc/watertight.hpp).  replaces: export_to_watertight (mesh_to_pc.py:13-40), i.e.
+ * mesh2sdf.core.compute + skimage.measure.marching_cubes(np.abs(sdf), level).  Needs no engine; errors via ma_last_error(NULL).
+ *
+ * ma_op_mesh_udf: unsigned distance to a triangle mesh on a size^3 grid, field (size, size, size) fp32 with axes x, y, z; grid point
+ *   (i, j, k) sits at -1 + 2 * (i, j, k) / size.  verts (nv, 3) fp32 and faces (nf, 3) int32 are device arrays; vertices must be finite
+ *   (the caller checks).  Narrow band: every grid point within 2 cells of a triangle's index-space bounding box holds the fp32
+ *   distance minimum over those triangles, every other point +inf; so every point closer than 2 * (2 / size) to the mesh is exact.
+ *   A face whose inradius is below 1/128 of a cell (collinear or near-collinear) counts as its three edges: off by at most its inradius.
+ *   Bitwise reproducible.  2 <= size <= 512, 1 <= nf <= MA_MESH_UDF_MAX_FACES.  workspace: ma_mesh_udf_workspace_bytes(nf) bytes of
+ *   device memory (0 for an nf outside that range). */
+#define MA_MESH_UDF_MAX_FACES (1 << 28)
+MA_API int  ma_op_mesh_udf(const float *verts, int nv, const int32_t *faces, int nf, int size, float *field, void *workspace, size_t ws_bytes,
+                           void *stream);
+MA_API size_t ma_mesh_udf_workspace_bytes(int nf);
+/* ma_op_marching_cubes: the level set field == level of a (nx, ny, nz) fp32 grid (C order).  verts (max_verts, 3) fp32 in index space
+ *   (as skimage returns them), one per grid edge that crosses the level, placed by linear interpolation; tris (max_tris, 3) int32 vertex
+ *   ids in cell-linear order, table order inside a cell, each normal (b - a) x (c - a) pointing toward increasing values.
+ *   counts: host int64[2] = {vertices, triangles}, always written.  verts == tris == NULL: count only.  A result larger than
+ *   max_verts / max_tris: MA_ERR_CAPACITY, nothing written.  Synchronises `stream`.  workspace: ma_marching_cubes_workspace_bytes. */
+MA_API int  ma_op_marching_cubes(const float *field, int nx, int ny, int nz, float level, float *verts, int64_t max_verts, int32_t *tris,
+                                 int64_t max_tris, int64_t *counts, void *workspace, size_t ws_bytes, void *stream);
+MA_API size_t ma_marching_cubes_workspace_bytes(int nx, int ny, int nz);
+/* host only: the marching-cubes table the kernel reads.  tris: 256 * 3 * max_tris_per_cell int8 (edge ids, -1 padded), edges: 12 * 4
+ *   int8 (corner offset dx, dy, dz, axis); corner c of a cell is at (c & 1, c >> 1 & 1, c >> 2 & 1), bit c of a case is set when that
+ *   corner is >= level.  Any pointer may be NULL (ask for max_tris_per_cell first). */
+MA_API int  ma_mc_table(int8_t *tris, int8_t *edges, int32_t *max_tris_per_cell);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@
 Same flags as the reference.  Differences, all forced by the environment (no network, no trimesh): the checkpoint is
 read from `--pretrained_weights` (the reference ignores that flag and downloads `MeshAnything_350m.pth`, main.py:95-98;
 `--synthetic_weights` uses the seeded random checkpoint of the tests instead); `--input_type mesh` reads .obj / .ply / .off /
-.stl and samples the surface in numpy (`meshanything_amd/mesh_input.py`), `--mc` is refused (needs mesh2sdf + scikit-image); the
+.stl and samples the surface in numpy (`meshanything_amd/mesh_input.py`), `--mc` makes the input watertight on the GPU first
+(`meshanything_amd/watertight.py`: unsigned distance + marching cubes in HIP instead of mesh2sdf + scikit-image); the
 mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
@@ -46,7 +47,7 @@ def get_args():
 def main():
     from meshanything_amd import dp
     from meshanything_amd.checkpoint import load_safetensors_items, synthetic_items
-    from meshanything_amd.data import Dataset
+    from meshanything_amd.data import Dataset, uid_of
     from meshanything_amd.mesh_export import faces_from_coords, fix_normals, write_obj
     from meshanything_amd.model import MeshAnything
 
@@ -75,7 +76,17 @@ def main():
         raise ValueError("input_dir or input_path must be provided.")
     np.random.seed(args.seed)                    # accelerate.set_seed(args.seed) before Dataset (main.py:129-133)
     torch.manual_seed(args.seed)
-    dataset = Dataset(args.input_type, input_list, args.mc)
+    if args.input_type == "mesh" and args.mc:
+        # main.py:29-39 with --mc: every rank remeshes every input, in file order, so that the global numpy RNG is consumed as in a
+        # one-process run (the sampling draws from it after each shape)
+        from meshanything_amd.mesh_input import load_mesh
+        from meshanything_amd.watertight import process_mesh_to_pc
+        meshes = [load_mesh(p) for p in input_list]
+        print("First Marching Cubes and then sample point cloud, need several minutes...")
+        pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True)
+        dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
+    else:
+        dataset = Dataset(args.input_type, input_list, args.mc)
 
     begin = time.time()
     print("Generation Start!!!")

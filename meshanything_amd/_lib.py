@@ -19,8 +19,10 @@ def _on(var: str) -> bool:
 LIB_PATH = os.path.join(HERE, "libmeshanything_amd" + ("_debug" if _on("MA_DEBUG") else "") + ("_exp" if _on("MA_EXPERIMENTAL") else "") + ".so")
 
 MA_OK = 0
+MA_ERR_CAPACITY = -8
 ERR_NAMES = {0: "MA_OK", -1: "MA_ERR_INVALID", -2: "MA_ERR_HIP", -3: "MA_ERR_STATE", -4: "MA_ERR_UNKNOWN_TENSOR",
-             -5: "MA_ERR_SHAPE", -6: "MA_ERR_MISSING", -7: "MA_ERR_NCCL"}
+             -5: "MA_ERR_SHAPE", -6: "MA_ERR_MISSING", -7: "MA_ERR_NCCL",
+             -8: "MA_ERR_CAPACITY"}
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -94,6 +96,11 @@ SIGNATURES = {
     "ma_engine_persist_available": (_I, [_P]),
     "ma_persist_trace": (_I, [_P, _I, _P, C.POINTER(C.c_int32), _P]),
     "ma_engine_read_logits": (_I, [_P, _I, _P, _P]),
+    "ma_op_mesh_udf": (_I, [_P, _I, _P, _I, _I, _P, _P, C.c_size_t, _P]),
+    "ma_mesh_udf_workspace_bytes": (C.c_size_t, [_I]),
+    "ma_op_marching_cubes": (_I, [_P, _I, _I, _I, _F, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_size_t, _P]),
+    "ma_marching_cubes_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "ma_mc_table": (_I, [_P, _P, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -35,6 +35,7 @@
 #include "rows_attn.hpp"
 #include "rows_mlp.hpp"
 #include "state.hpp"
+#include "watertight.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -2469,5 +2470,59 @@ int ma_engine_read_logits(ma_engine* e, int row, float* out, void* stream) {
 
 // 1 when the persistent decode step can run on this engine (bf16, 350M layer shape, 256-CU device), else 0
 int ma_engine_persist_available(ma_engine* e) { return e && e->persist_shape ? 1 : 0; }
+
+// ---- watertight remeshing (csrc/watertight.hpp) -----------------------------------------------------------------------------
+size_t ma_mesh_udf_workspace_bytes(int nf) { return nf < 1 || nf > MA_MESH_UDF_MAX_FACES ? 0 : wt::udf_ws_bytes(nf); }
+
+int ma_op_mesh_udf(const float* verts, int nv, const int32_t* faces, int nf, int size, float* field, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!verts || !faces || !field || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_mesh_udf: null pointer");
+        if (nv < 1 || nf < 1 || nf > MA_MESH_UDF_MAX_FACES || size < 2 || size > 512)
+            throw MaError(MA_ERR_INVALID, "ma_op_mesh_udf: need nv >= 1, 1 <= nf <= 2^28 and size in [2, 512]");
+        if (ws_bytes < wt::udf_ws_bytes(nf)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_udf: workspace smaller than ma_mesh_udf_workspace_bytes(nf)");
+        HIP_CHECK(wt::launch_mesh_udf(verts, nv, faces, nf, size, field, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+size_t ma_marching_cubes_workspace_bytes(int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return 0;
+    return wt::mc_ws_bytes((int64_t)nx * ny * nz);
+}
+
+int ma_op_marching_cubes(const float* field, int nx, int ny, int nz, float level, float* verts, int64_t max_verts, int32_t* tris, int64_t max_tris,
+                         int64_t* counts, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!field || !counts || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: null field, counts or workspace");
+        if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny * nz > (int64_t(1) << 30))
+            throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: need nx, ny, nz >= 2 and at most 2^30 grid points");
+        if (!std::isfinite(level)) throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: non-finite level");
+        if ((verts == nullptr) != (tris == nullptr)) throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: verts and tris must both be given or both be NULL");
+        const int64_t np = (int64_t)nx * ny * nz;
+        if (ws_bytes < wt::mc_ws_bytes(np)) throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: workspace smaller than ma_marching_cubes_workspace_bytes(nx, ny, nz)");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        wt::McWs ws;
+        wt::mc_ws_bytes(np, &ws, workspace);
+        HIP_CHECK(wt::launch_mc_count(field, nx, ny, nz, level, ws, s));
+        int64_t tot[2];
+        HIP_CHECK(hipMemcpyAsync(&tot[0], ws.vcount + np, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&tot[1], ws.tcount + np, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        counts[0] = tot[0];
+        counts[1] = tot[1];
+        if (tot[0] > INT32_MAX) throw MaError(MA_ERR_INVALID, "ma_op_marching_cubes: more than 2^31 - 1 vertices");
+        if (!verts) return;
+        if (tot[0] > max_verts || tot[1] > max_tris)
+            throw MaError(MA_ERR_CAPACITY, "ma_op_marching_cubes: " + std::to_string(tot[0]) + " vertices / " + std::to_string(tot[1]) +
+                                               " triangles do not fit in max_verts " + std::to_string(max_verts) + " / max_tris " + std::to_string(max_tris));
+        HIP_CHECK(wt::launch_mc_emit(field, nx, ny, nz, level, ws, verts, max_verts, tris, max_tris, s));
+    });
+}
+
+int ma_mc_table(int8_t* tris, int8_t* edges, int32_t* max_tris_per_cell) {
+    if (max_tris_per_cell) *max_tris_per_cell = wt::MC_MAX_TRIS;
+    if (tris) std::memcpy(tris, wt::MC_TRIS_HOST, sizeof(wt::MC_TRIS_HOST));
+    if (edges) std::memcpy(edges, wt::MC_EDGES_HOST, sizeof(wt::MC_EDGES_HOST));
+    return MA_OK;
+}
 
 }  // extern "C"

@@ -20,6 +20,11 @@ def normalize_pc(pc_normal: np.ndarray) -> np.ndarray:
     return np.concatenate([pc_coor, normals], axis=-1, dtype=np.float16)
 
 
+def uid_of(input_path: str) -> str:
+    """main.py:27,39: the sample's name, the file name up to its first dot."""
+    return input_path.split("/")[-1].split(".")[0]
+
+
 class Dataset:
     """`Dataset('pc_normal' | 'mesh', paths)` of main.py:15-58.  Sampling uses the GLOBAL numpy RNG like the reference
     (seed it first: main.py:129-133 calls accelerate.set_seed(args.seed) -> np.random.seed)."""
@@ -32,18 +37,30 @@ class Dataset:
                 assert cur_data.shape[0] >= n_points, "input pc_normal should have at least 4096 points"
                 idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
                 cur_data = cur_data[idx]
-                self.data.append({"pc_normal": cur_data, "uid": input_path.split("/")[-1].split(".")[0]})
+                self.data.append({"pc_normal": cur_data, "uid": uid_of(input_path)})
         elif input_type == "mesh":
             # main.py:29-39 -> mesh_to_pc.py:42-57: load the file, draw n_points surface points + the normal of the face under each
             from .mesh_input import load_mesh, mesh_to_pc_normal
             if mc:
-                raise NotImplementedError("--mc (mesh_to_pc.py:13-40: mesh2sdf signed distances + scikit-image marching cubes to make the "
-                                          "input watertight before sampling) needs mesh2sdf and scikit-image, which are not installed")
+                raise NotImplementedError("--mc (mesh_to_pc.py:13-40: make the input watertight before sampling) runs on the GPU and this "
+                                          "Dataset is host-only: run meshanything_amd.watertight.process_mesh_to_pc(meshes, "
+                                          "marching_cubes=True) and build the dataset with Dataset.from_clouds(clouds, uids)")
             for input_path in input_list:
                 vertices, faces = load_mesh(input_path)
-                self.data.append({"pc_normal": mesh_to_pc_normal(vertices, faces, n_points), "uid": input_path.split("/")[-1].split(".")[0]})
+                self.data.append({"pc_normal": mesh_to_pc_normal(vertices, faces, n_points), "uid": uid_of(input_path)})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
         print(f"dataset total data samples: {len(self.data)}")
+
+    @classmethod
+    def from_clouds(cls, clouds: List[np.ndarray], uids: List[str]) -> "Dataset":
+        """The dataset of already sampled (N, 6) clouds, e.g. the output of watertight.process_mesh_to_pc(..., marching_cubes=True)
+        (main.py:29-39 with --mc); items are normalised on access exactly like the constructor's."""
+        if len(clouds) != len(uids):
+            raise ValueError(f"{len(clouds)} clouds but {len(uids)} uids")
+        self = cls.__new__(cls)
+        self.data = [{"pc_normal": c, "uid": u} for c, u in zip(clouds, uids)]
+        print(f"dataset total data samples: {len(self.data)}")
+        return self
 
     def __len__(self) -> int:
         return len(self.data)

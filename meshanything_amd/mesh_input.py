@@ -18,8 +18,10 @@ cloud as this package's own, statistically equivalent, not draw-for-draw equal. 
 (tests/test_mesh_input.py) are the properties the rest of the path relies on: points on the surface, unit normals of the face under
 each point, density proportional to area, identical geometry through every file format.
 
-`--mc` (mesh2sdf + marching cubes to make the input watertight first, mesh_to_pc.py:13-40) needs mesh2sdf and scikit-image, neither
-of which is installed: it raises NotImplementedError with that explanation.
+`--mc` (make the input watertight first, mesh_to_pc.py:13-40: mesh2sdf distances + scikit-image marching cubes) is
+`watertight.process_mesh_to_pc(meshes, marching_cubes=True)`: the distance field and the marching cubes run as HIP kernels, the result
+is sampled here.  `Dataset('mesh', paths, mc=True)` stays host-only and refuses it (NotImplementedError naming that function);
+main.py runs the GPU step and builds the dataset with `Dataset.from_clouds`.  Its parity is unpinned too (watertight.py says how).
 """
 from __future__ import annotations
 
