@@ -334,6 +334,34 @@ MA_API size_t ma_marching_cubes_workspace_bytes(int nx, int ny, int nz);
  *   corner is >= level.  Any pointer may be NULL (ask for max_tris_per_cell first). */
 MA_API int  ma_mc_table(int8_t *tris, int8_t *edges, int32_t *max_tris_per_cell);
 
+/* ---- surface sampling of a mesh (csrc/surface_sample.hpp).  replaces: mesh.sample(n, return_index=True) + face_normals[face_idx]
+ * (mesh_to_pc.py:50-54), i.e. mesh_input.mesh_to_pc_normal.  Needs no engine; errors via ma_last_error(NULL); every argument is checked
+ * before the first launch.  Device arrays, caller-owned workspace, asynchronous on `stream`.  All arithmetic is float64 in numpy's
+ * order without FMA contraction, so for the same draws the output is mesh_input.py's bit for bit, except that the cumulative sum of
+ * the areas is a parallel scan: it may round differently from np.cumsum, which can move a draw that lands within that rounding of
+ * a face boundary to the neighbouring face.
+ *
+ * ma_op_mc_vertices_to_frame: verts (nv, 3) float64 = ((double(index_verts) / size) * 2 - 1) / to_orig_scale + center (host double[3]),
+ *   the marching-cubes output of ma_op_marching_cubes mapped back to the input's frame (watertight.export_to_watertight).
+ * ma_op_surface_cdf: per face of verts (nv, 3) float64 / faces (nf, 3) int32, the unit normal (normals (nf, 3) float64, 0 for a
+ *   zero-area face) and the cumulative area (cum (nf) float64, non-decreasing, unchanged across a zero-area face); cum[nf - 1] is the
+ *   total area, which the caller reads back and checks (> 0) before it draws.  workspace: ma_surface_sample_workspace_bytes(nf) bytes
+ *   (0 for an nf outside [1, MA_SURFACE_SAMPLE_MAX_FACES]).
+ * ma_op_sample_surface: `count` points from the draws u (count) and uv (count, 2) in [0, 1): face = the first j with
+ *   cum[j] > u * cum[nf - 1] (at most nf - 1), (a, b) = uv folded to (1 - a, 1 - b) when a + b > 1, point = (t0 + a (t1 - t0)) +
+ *   b (t2 - t0); out (count, 6) float16 = point, normals[face], each correctly rounded from float64; face_idx (count) int64 or NULL. */
+#define MA_SURFACE_SAMPLE_MAX_FACES (1 << 28)
+MA_API int  ma_op_mc_vertices_to_frame(const float *index_verts, int nv, int size, double to_orig_scale, const double *center, double *verts,
+                                       void *stream);
+MA_API int  ma_op_surface_cdf(const double *verts, int nv, const int32_t *faces, int nf, double *normals, double *cum, void *workspace,
+                              size_t ws_bytes, void *stream);
+MA_API size_t ma_surface_sample_workspace_bytes(int nf);
+MA_API int  ma_op_sample_surface(const double *verts, int nv, const int32_t *faces, int nf, const double *normals, const double *cum,
+                                 const double *u, const double *uv, int count, uint16_t *out, int64_t *face_idx, void *stream);
+/* host only: out[i] = float16 bits of x[i], rounded to nearest even in one step (numpy's astype(float16)): the conversion
+ *   ma_op_sample_surface applies, exposed so that it can be checked without a device. */
+MA_API int  ma_f64_to_f16(const double *x, int64_t n, uint16_t *out);
+
 #ifdef __cplusplus
 }
 #endif

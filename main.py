@@ -7,7 +7,8 @@
 Same flags as the reference.  Differences, all forced by the environment (no network, no trimesh): the checkpoint is
 read from `--pretrained_weights` (the reference ignores that flag and downloads `MeshAnything_350m.pth`, main.py:95-98;
 `--synthetic_weights` uses the seeded random checkpoint of the tests instead); `--input_type mesh` reads .obj / .ply / .off /
-.stl and samples the surface in numpy (`meshanything_amd/mesh_input.py`), `--mc` makes the input watertight on the GPU first
+.stl and samples the surface in numpy (`meshanything_amd/mesh_input.py`; with the extra flag `--gpu_sampling` the same samples come from
+HIP kernels, `meshanything_amd/surface_sample.py`), `--mc` makes the input watertight on the GPU first
 (`meshanything_amd/watertight.py`: unsigned distance + marching cubes in HIP instead of mesh2sdf + scikit-image); the
 mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
@@ -40,6 +41,8 @@ def get_args():
     p.add_argument("--mc", default=False, action="store_true")
     p.add_argument("--sampling", default=False, action="store_true")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    p.add_argument("--gpu_sampling", default=False, action="store_true",
+                   help="sample mesh inputs (and the --mc surface) on the GPU: the same draws and clouds as the host sampler")
     p.add_argument("--synthetic_weights", default=False, action="store_true", help="seeded random checkpoint (no released file offline)")
     return p.parse_args()
 
@@ -76,6 +79,7 @@ def main():
         raise ValueError("input_dir or input_path must be provided.")
     np.random.seed(args.seed)                    # accelerate.set_seed(args.seed) before Dataset (main.py:129-133)
     torch.manual_seed(args.seed)
+    sample_device = "cuda" if args.gpu_sampling else None     # the current device: torch.cuda.set_device(local) above
     if args.input_type == "mesh" and args.mc:
         # main.py:29-39 with --mc: every rank remeshes every input, in file order, so that the global numpy RNG is consumed as in a
         # one-process run (the sampling draws from it after each shape)
@@ -83,10 +87,10 @@ def main():
         from meshanything_amd.watertight import process_mesh_to_pc
         meshes = [load_mesh(p) for p in input_list]
         print("First Marching Cubes and then sample point cloud, need several minutes...")
-        pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True)
+        pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True, device=sample_device)
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
-        dataset = Dataset(args.input_type, input_list, args.mc)
+        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device)
 
     begin = time.time()
     print("Generation Start!!!")

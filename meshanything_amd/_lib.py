@@ -101,6 +101,11 @@ SIGNATURES = {
     "ma_op_marching_cubes": (_I, [_P, _I, _I, _I, _F, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_size_t, _P]),
     "ma_marching_cubes_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ma_mc_table": (_I, [_P, _P, C.POINTER(C.c_int32)]),
+    "ma_op_mc_vertices_to_frame": (_I, [_P, _I, _I, C.c_double, _P, _P, _P]),
+    "ma_op_surface_cdf": (_I, [_P, _I, _P, _I, _P, _P, _P, C.c_size_t, _P]),
+    "ma_surface_sample_workspace_bytes": (C.c_size_t, [_I]),
+    "ma_op_sample_surface": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "ma_f64_to_f16": (_I, [_P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -35,6 +35,7 @@
 #include "rows_attn.hpp"
 #include "rows_mlp.hpp"
 #include "state.hpp"
+#include "surface_sample.hpp"
 #include "watertight.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
@@ -2522,6 +2523,45 @@ int ma_mc_table(int8_t* tris, int8_t* edges, int32_t* max_tris_per_cell) {
     if (max_tris_per_cell) *max_tris_per_cell = wt::MC_MAX_TRIS;
     if (tris) std::memcpy(tris, wt::MC_TRIS_HOST, sizeof(wt::MC_TRIS_HOST));
     if (edges) std::memcpy(edges, wt::MC_EDGES_HOST, sizeof(wt::MC_EDGES_HOST));
+    return MA_OK;
+}
+
+
+// ---- surface sampling (csrc/surface_sample.hpp) -----------------------------------------------------------------------------
+size_t ma_surface_sample_workspace_bytes(int nf) { return nf < 1 || nf > MA_SURFACE_SAMPLE_MAX_FACES ? 0 : ss::cdf_ws_bytes(nf); }
+
+int ma_op_mc_vertices_to_frame(const float* index_verts, int nv, int size, double to_orig_scale, const double* center, double* verts, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!index_verts || !center || !verts) throw MaError(MA_ERR_INVALID, "ma_op_mc_vertices_to_frame: null pointer");
+        if (nv < 1 || size < 1) throw MaError(MA_ERR_INVALID, "ma_op_mc_vertices_to_frame: need nv >= 1 and size >= 1");
+        if (!std::isfinite(to_orig_scale) || !(to_orig_scale != 0.0)) throw MaError(MA_ERR_INVALID, "ma_op_mc_vertices_to_frame: to_orig_scale must be finite and non-zero");
+        HIP_CHECK(ss::launch_frame(index_verts, nv, size, to_orig_scale, center, verts, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_surface_cdf(const double* verts, int nv, const int32_t* faces, int nf, double* normals, double* cum, void* workspace, size_t ws_bytes,
+                      void* stream) {
+    return guarded(nullptr, [&] {
+        if (!verts || !faces || !normals || !cum || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_surface_cdf: null pointer");
+        if (nv < 1 || nf < 1 || nf > MA_SURFACE_SAMPLE_MAX_FACES) throw MaError(MA_ERR_INVALID, "ma_op_surface_cdf: need nv >= 1 and 1 <= nf <= 2^28");
+        if (ws_bytes < ss::cdf_ws_bytes(nf)) throw MaError(MA_ERR_INVALID, "ma_op_surface_cdf: workspace smaller than ma_surface_sample_workspace_bytes(nf)");
+        HIP_CHECK(ss::launch_surface_cdf(verts, nv, faces, nf, normals, cum, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_sample_surface(const double* verts, int nv, const int32_t* faces, int nf, const double* normals, const double* cum, const double* u,
+                         const double* uv, int count, uint16_t* out, int64_t* face_idx, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!verts || !faces || !normals || !cum || !u || !uv || !out) throw MaError(MA_ERR_INVALID, "ma_op_sample_surface: null pointer");
+        if (nv < 1 || nf < 1 || nf > MA_SURFACE_SAMPLE_MAX_FACES || count < 1)
+            throw MaError(MA_ERR_INVALID, "ma_op_sample_surface: need nv >= 1, 1 <= nf <= 2^28 and count >= 1");
+        HIP_CHECK(ss::launch_draw(verts, nv, faces, nf, normals, cum, u, uv, count, out, face_idx, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_f64_to_f16(const double* x, int64_t n, uint16_t* out) {
+    if (!x || !out || n < 0) return MA_ERR_INVALID;
+    for (int64_t i = 0; i < n; ++i) out[i] = ss::f64_to_f16_rne(x[i]);
     return MA_OK;
 }
 

@@ -27,9 +27,10 @@ def uid_of(input_path: str) -> str:
 
 class Dataset:
     """`Dataset('pc_normal' | 'mesh', paths)` of main.py:15-58.  Sampling uses the GLOBAL numpy RNG like the reference
-    (seed it first: main.py:129-133 calls accelerate.set_seed(args.seed) -> np.random.seed)."""
+    (seed it first: main.py:129-133 calls accelerate.set_seed(args.seed) -> np.random.seed).  sample_device (e.g. "cuda"): sample
+    mesh inputs on that GPU (mesh_input.mesh_to_pc_normal(..., device=...)): the same draws, the same clouds."""
 
-    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096):
+    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None):
         self.data: List[Dict] = []
         if input_type == "pc_normal":
             for input_path in input_list:
@@ -47,7 +48,7 @@ class Dataset:
                                           "marching_cubes=True) and build the dataset with Dataset.from_clouds(clouds, uids)")
             for input_path in input_list:
                 vertices, faces = load_mesh(input_path)
-                self.data.append({"pc_normal": mesh_to_pc_normal(vertices, faces, n_points), "uid": uid_of(input_path)})
+                self.data.append({"pc_normal": mesh_to_pc_normal(vertices, faces, n_points, device=sample_device), "uid": uid_of(input_path)})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
         print(f"dataset total data samples: {len(self.data)}")
 

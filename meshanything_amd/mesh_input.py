@@ -20,8 +20,13 @@ each point, density proportional to area, identical geometry through every file 
 
 `--mc` (make the input watertight first, mesh_to_pc.py:13-40: mesh2sdf distances + scikit-image marching cubes) is
 `watertight.process_mesh_to_pc(meshes, marching_cubes=True)`: the distance field and the marching cubes run as HIP kernels, the result
-is sampled here.  `Dataset('mesh', paths, mc=True)` stays host-only and refuses it (NotImplementedError naming that function);
-main.py runs the GPU step and builds the dataset with `Dataset.from_clouds`.  Its parity is unpinned too (watertight.py says how).
+is sampled here, or with `device="cuda"` on the GPU.  `Dataset('mesh', paths, mc=True)` refuses it (NotImplementedError naming that
+function); main.py runs the GPU step and builds the dataset with `Dataset.from_clouds`.  Its parity is unpinned too (watertight.py says how).
+
+Opt-in GPU sampling: `mesh_to_pc_normal(..., device="cuda")` (surface_sample.py, `main.py --gpu_sampling`) runs this module's float64
+arithmetic as HIP kernels on the same draws from the global RNG, so it returns the same float16 cloud bit for bit and leaves the RNG in
+the same state; only the cumulative sum of the areas rounds differently (a parallel scan), which can matter only for a draw within
+that rounding of a face boundary.
 """
 from __future__ import annotations
 
@@ -218,9 +223,16 @@ def sample_surface(vertices: np.ndarray, faces: np.ndarray, count: int) -> Tuple
     return points, face_idx
 
 
-def mesh_to_pc_normal(vertices: np.ndarray, faces: np.ndarray, sample_num: int = 4096) -> np.ndarray:
+def mesh_to_pc_normal(vertices: np.ndarray, faces: np.ndarray, sample_num: int = 4096, device=None) -> np.ndarray:
     """One mesh of `process_mesh_to_pc(mesh_list, marching_cubes=False)` (mesh_to_pc.py:42-57): (sample_num, 6) float16 =
-    surface points + the normal of the face under each."""
+    surface points + the normal of the face under each.
+
+    device (e.g. "cuda"): the same computation as HIP kernels on that GPU (surface_sample.py): the same draws from the global RNG,
+    the same cloud (up to a draw within rounding of a face boundary, see there), the same ValueError for a mesh without area; the
+    mesh is checked first (watertight.check_mesh).  None (the default): numpy, as above."""
+    if device is not None:
+        from .surface_sample import mesh_to_pc_normal as on_device
+        return on_device(vertices, faces, sample_num, device)
     points, face_idx = sample_surface(vertices, faces, sample_num)
     normals, _ = face_normals_and_areas(vertices, faces)
     return np.concatenate([points, normals[face_idx]], axis=-1, dtype=np.float16)

@@ -2,7 +2,8 @@
 
 `export_to_watertight` normalises the mesh into [-0.9, 0.9]^3, computes the distance to it on a 128^3 grid and extracts the level
 set |sdf| = 2 / 128 by marching cubes: a closed two-sheet shell one cell either side of the input surface, mapped back to the input's
-frame.  `process_mesh_to_pc` then samples 4096 points + face normals of it like any other mesh input (mesh_input.mesh_to_pc_normal).
+frame.  `process_mesh_to_pc` then samples 4096 points + face normals of it like any other mesh input (mesh_input.mesh_to_pc_normal);
+with `device="cuda"` the marching-cubes output stays on the GPU and is sampled there (surface_sample.py), giving the same clouds.
 
 The reference computes a SIGNED distance with mesh2sdf and runs scikit-image's Lewiner marching cubes on the CPU ("need several
 minutes").  Only |sdf| is used there, so this package computes the unsigned distance directly, in a narrow band of two cells around
@@ -39,9 +40,9 @@ def normalize_vertices(vertices: np.ndarray, scale: float = 0.9):
     return vertices, center, scale
 
 
-def check_mesh(vertices, faces) -> Mesh:
+def check_mesh(vertices, faces, need_extent: bool = True) -> Mesh:
     """The input checks of the GPU path, before anything is launched: ValueError for an empty mesh, a non-finite vertex, a face
-    index out of range or a mesh without extent.  Returns (vertices float64 (V, 3), faces int64 (F, 3))."""
+    index out of range or (need_extent) a mesh without extent.  Returns (vertices float64 (V, 3), faces int64 (F, 3))."""
     v = np.asarray(vertices, dtype=np.float64)
     f = np.asarray(faces)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
@@ -57,7 +58,7 @@ def check_mesh(vertices, faces) -> Mesh:
         raise ValueError(f"a face refers to vertex {int(f.min()) if f.min() < 0 else int(f.max())}, the mesh has {v.shape[0]}")
     if v.shape[0] >= 2 ** 31 or f.shape[0] > 2 ** 28:
         raise ValueError("meshes with 2^31 or more vertices or more than 2^28 faces are not supported")
-    if not (v.max(0) - v.min(0)).max() > 0:
+    if need_extent and not (v.max(0) - v.min(0)).max() > 0:
         raise ValueError("the mesh has no extent (all vertices coincide)")
     return v, f
 
@@ -86,6 +87,14 @@ def mesh_udf(vertices: np.ndarray, faces: np.ndarray, size: int):
 def extract_level_set(field, level: float, count_only: bool = False):
     """The level set `field == level` of a float32 CUDA tensor (nx, ny, nz) (ma_op_marching_cubes): vertices (V, 3) float32 in index
     space and triangles (F, 3) int32, as numpy arrays; each triangle's normal points toward increasing values.  count_only: (V, F)."""
+    if count_only:
+        return _level_set(field, level, True)
+    verts, tris = _level_set(field, level)
+    return verts.cpu().numpy(), tris.cpu().numpy()
+
+
+def _level_set(field, level: float, count_only: bool = False):
+    """extract_level_set, leaving the vertices and triangles on the device (torch tensors)."""
     import torch
     if field.dtype != torch.float32 or field.dim() != 3 or not field.is_cuda:
         raise ValueError("field must be a 3-D float32 CUDA tensor")
@@ -103,36 +112,61 @@ def extract_level_set(field, level: float, count_only: bool = False):
     tris = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=field.device)
     _lib.check(lib.ma_op_marching_cubes(field.data_ptr(), nx, ny, nz, float(level), verts.data_ptr(), nv, tris.data_ptr(), nt, counts,
                                         ws.data_ptr(), nbytes, _stream()))
-    return verts[:nv].cpu().numpy(), tris[:nt].cpu().numpy()
+    return verts[:nv], tris[:nt]
 
 
-def export_to_watertight(vertices, faces, octree_depth: int = 7) -> Mesh:
-    """mesh_to_pc.py:13-40 on the GPU: the closed shell |distance| = 2 / 2^octree_depth around the normalised mesh, in the input's
-    frame.  Returns (vertices float64 (V, 3), faces int64 (F, 3)); face winding gives outward normals on the outer sheet."""
+def _watertight_on_device(vertices, faces, octree_depth: int = 7):
+    """export_to_watertight up to the marching cubes: (index-space vertices (V, 3) float32 and triangles (F, 3) int32 as CUDA tensors,
+    size, to_orig_center, to_orig_scale)."""
     v, f = check_mesh(vertices, faces)
     size = 2 ** octree_depth
     level = 2 / size
     scaled_vertices, to_orig_center, to_orig_scale = normalize_vertices(v)
     field = mesh_udf(scaled_vertices, f, size)
-    mv, mf = extract_level_set(field, level)
+    mv, mf = _level_set(field, level)
     if mf.shape[0] == 0:
         raise ValueError("marching cubes found no surface")
+    return mv, mf, size, to_orig_center, to_orig_scale
+
+
+def export_to_watertight(vertices, faces, octree_depth: int = 7) -> Mesh:
+    """mesh_to_pc.py:13-40 on the GPU: the closed shell |distance| = 2 / 2^octree_depth around the normalised mesh, in the input's
+    frame.  Returns (vertices float64 (V, 3), faces int64 (F, 3)); face winding gives outward normals on the outer sheet."""
+    mv, mf, size, to_orig_center, to_orig_scale = _watertight_on_device(vertices, faces, octree_depth)
+    mv, mf = mv.cpu().numpy(), mf.cpu().numpy()
     mv = mv.astype(np.float64) / size * 2 - 1                     # -1 to 1
     mv = mv / to_orig_scale + to_orig_center
     return mv, mf.astype(np.int64)
 
 
-def process_mesh_to_pc(mesh_list: Sequence[Mesh], marching_cubes: bool = False, sample_num: int = 4096) -> Tuple[List[np.ndarray], List[Mesh]]:
+def process_mesh_to_pc(mesh_list: Sequence[Mesh], marching_cubes: bool = False, sample_num: int = 4096,
+                       device=None) -> Tuple[List[np.ndarray], List[Mesh]]:
     """mesh_to_pc.py:42-57: for each (vertices, faces) mesh, optionally made watertight first, `sample_num` surface points + the normal
-    of the face under each, (sample_num, 6) float16, drawn from the global numpy RNG.  Returns (pc_normal_list, mesh_list)."""
+    of the face under each, (sample_num, 6) float16, drawn from the global numpy RNG.  Returns (pc_normal_list, mesh_list).
+
+    device (e.g. "cuda"): sample on that GPU (surface_sample.py), with the same draws and the same clouds; with marching_cubes the
+    remeshed surface stays on the device between the marching cubes and the sampling.  The returned meshes are the same host arrays."""
     if marching_cubes:
         mesh_list = [check_mesh(v, f) for v, f in mesh_list]      # every input checked before the first launch
+    if device is not None:
+        from . import surface_sample
+        dev = surface_sample.cuda_device(device)
     pc_normal_list, return_mesh_list = [], []
     for vertices, faces in mesh_list:
+        if marching_cubes and device is not None:
+            import torch
+            with torch.cuda.device(dev):
+                mv, mf, size, center, scale = _watertight_on_device(vertices, faces)
+                print("MC over!")
+                pc, (vertices, faces) = surface_sample.watertight_pc_normal(mv, mf, size, center, scale, sample_num)
+            return_mesh_list.append((vertices, faces))
+            pc_normal_list.append(pc)
+            print("process mesh success")
+            continue
         if marching_cubes:
             vertices, faces = export_to_watertight(vertices, faces)
             print("MC over!")
         return_mesh_list.append((vertices, faces))
-        pc_normal_list.append(mesh_to_pc_normal(vertices, faces, sample_num))
+        pc_normal_list.append(mesh_to_pc_normal(vertices, faces, sample_num, device=device))
         print("process mesh success")
     return pc_normal_list, return_mesh_list

@@ -6,7 +6,10 @@ For three procedural meshes up to ~200k faces, the median over `reps` runs (afte
 (ma_op_mesh_udf), the marching-cubes count (ma_op_marching_cubes without outputs: classify + two scans + the count read-back), the
 marching-cubes count + emit (the same call with outputs; emit alone = the difference), each timed with HIP events on the current stream
 (the count read-back synchronises the stream inside the call, so those two are host-synchronous anyway), and the host-side sampling
-of 4096 points on the result (numpy, wall clock).  One JSON line per mesh.  DESIGN.md section 8 records the numbers.
+of 4096 points on the result (numpy, wall clock).  The GPU sampling stage (surface_sample.py) of the same 4096 points: its kernels
+(frame + cdf + draw, on draws already on the device) with HIP events, and the whole call as `process_mesh_to_pc(..., device=...)` makes
+it (frame, cdf, total read-back, draws taken and uploaded, sample, cloud and mesh read back) by wall clock; the cloud is checked
+against the host one on the same seed.  One JSON line per mesh.  DESIGN.md section 8 records the numbers.
 """
 import argparse
 import ctypes as C
@@ -20,7 +23,7 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
-from meshanything_amd import _lib, watertight  # noqa: E402
+from meshanything_amd import _lib, surface_sample, watertight  # noqa: E402
 from meshanything_amd.mesh_input import mesh_to_pc_normal  # noqa: E402
 import watertight_ref as W  # noqa: E402
 
@@ -82,7 +85,7 @@ def main():
             _lib.check(lib.ma_op_marching_cubes(field.data_ptr(), size, size, size, level, mv.data_ptr(), nv, mt.data_ptr(), nt, counts,
                                                 mws.data_ptr(), mnb, stream))
         t_full = median_ms(full, args.reps)
-        verts = mv.cpu().numpy().astype(np.float64) / size * 2 - 1
+        verts = mv.cpu().numpy().astype(np.float64) / size * 2 - 1          # sampled in this frame on the host (the area weights only scale)
         tris = mt.cpu().numpy().astype(np.int64)
         hs = []
         for r in range(max(3, args.reps // 4)):
@@ -90,9 +93,33 @@ def main():
             t0 = time.perf_counter()
             mesh_to_pc_normal(verts, tris, 4096)
             hs.append((time.perf_counter() - t0) * 1e3)
+        # GPU sampling of the same surface, in the input's frame as export_to_watertight gives it
+        _, center, scale = watertight.normalize_vertices(v)
+        cen = np.ascontiguousarray(center, dtype=np.float64)
+        fverts = torch.empty((nv, 3), dtype=torch.float64, device="cuda")
+        count = 4096
+        draws = torch.from_numpy(np.random.default_rng(0).random(3 * count)).cuda()
+
+        def kernels():
+            _lib.check(lib.ma_op_mc_vertices_to_frame(mv.data_ptr(), nv, size, float(scale), cen.ctypes.data, fverts.data_ptr(), stream))
+            normals, cum = surface_sample.surface_cdf(fverts, mt)
+            surface_sample.sample_draws(fverts, mt, normals, cum, draws, count)
+        t_kern = median_ms(kernels, args.reps)
+        gs = []
+        for r in range(max(3, args.reps // 4) + 2):
+            np.random.seed(r)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pc, _ = surface_sample.watertight_pc_normal(mv, mt, size, center, scale, count)
+            gs.append((time.perf_counter() - t0) * 1e3)
+        np.random.seed(r)
+        host_pc = mesh_to_pc_normal(verts / scale + center, tris, count)
+        same = bool(np.array_equal(pc.view(np.uint16), host_pc.view(np.uint16)))
         print(json.dumps({"mesh": name, "faces": int(f.shape[0]), "size": size, "mc_vertices": nv, "mc_triangles": nt,
                           "udf_ms": round(t_udf, 3), "mc_count_ms": round(t_count, 3), "mc_count_emit_ms": round(t_full, 3),
-                          "mc_emit_ms": round(t_full - t_count, 3), "host_sample_ms": round(float(np.median(hs)), 3)}), flush=True)
+                          "mc_emit_ms": round(t_full - t_count, 3), "host_sample_ms": round(float(np.median(hs)), 3),
+                          "gpu_sample_kernels_ms": round(t_kern, 3), "gpu_sample_call_ms": round(float(np.median(gs[2:])), 3),
+                          "gpu_sample_matches_host": same}), flush=True)
 
 
 if __name__ == "__main__":
