@@ -1,7 +1,7 @@
 // Persistent decode step: the whole batch-1 step (embedding -> 24 OPT layers -> lm_head -> greedy pick) as ONE launch.
 //
 // Reference path: the same 123 reference calls as the launch chain (shape_opt.py:318-364, 403-410, 155; [3p] OPTDecoderLayer,
-// GenerationMixin greedy).  The launch chain (engine.hip enqueue_decode_step) pays, per dependent op, a kernel boundary
+// GenerationMixin greedy).  The launch chain (engine_decode.hpp enqueue_decode_step) pays, per dependent op, a kernel boundary
 // (~1.35 us), a launch ramp, and a memory round trip for the input vector that queues behind the op's own weight stream.
 // Here one workgroup per CU stays resident for the whole step (recipe: MI355X guide, section "Persistent kernels" price list:
 // engine-vs-launches, prefetch-credit, allgather, nt-weights):
@@ -23,7 +23,7 @@
 // granule buffers are never cleared and a stale tag can never match.
 // Every wait is bounded (PS_TIMEOUT_TICKS of the 100 MHz real-time counter): on expiry the wave raises the block's abort word
 // and the engine's error word and leaves; the host turns that into an error after the burst.
-// Eligibility (engine.hip persist_eligible): bf16 policy, batch 1, greedy, hidden 1024 / ffn 4096 / 16 heads, 256 CUs.
+// Eligibility (engine_experimental.hpp persist_eligible): bf16 policy, batch 1, greedy, hidden 1024 / ffn 4096 / 16 heads, 256 CUs.
 #pragma once
 #include "../attn_decode.hpp"
 #include "../common.hpp"

@@ -18,7 +18,7 @@
 // bits of its batch-1 run -- the criterion of tests/test_gpu_rows_fused.py -- and, transitively, of the five-launch chain.
 // Protocol: the tagged-granule exchange of common.hpp (epoch = position * 32 + layer + 1, rows share the position), bounded sweeps, the
 // engine's error word; all 256 blocks must be resident (second launch: 130 KB of LDS, one block per CU) -- a starved grid times out
-// once and the engine re-runs the generation on the launch chain that needs no co-residency (engine.hip generate_batch).
+// once and the engine re-runs the generation on the launch chain that needs no co-residency (engine_generate.hpp generate_batch).
 // Reference: [3p] OPTDecoderLayer + OptFlashAttention2 reached from shape_opt.py:403-410 with a batch of rows (meshanything.py:143-162).
 #pragma once
 #include "../attn_decode.hpp"

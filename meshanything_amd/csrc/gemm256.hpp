@@ -57,7 +57,7 @@ constexpr int G256_EV = 2;
 // Order of every sum is fixed (4 columns of a lane, the DPP tree over 16 lanes, the four waves of a tile, the tiles in ascending order), so all tiles
 // of a row compute the same mean / rstd bit for bit and the result does not depend on timing.  The workgroups of a tile row are consecutive in the
 // tile list; a sweep is bounded like every in-launch exchange of this engine (20 ms, then the error word: the generation is re-run without the fused
-// forms, engine.hip generate_batch).  Whole tiles only, K not split.
+// forms, engine_generate.hpp generate_batch).  Whole tiles only, K not split.
 struct G256Ln {
     const float* gamma; const float* beta; float eps;
     u64* gran;                     // [2][nty * ntx][256]: row sums | sums of squared deviations, one granule per (tile, row)

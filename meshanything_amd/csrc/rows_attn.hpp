@@ -6,7 +6,7 @@
 // (row, head) and never leaves the 16 blocks of a head; attention -> out_proj is 64 values per (row, head), 16 KB for all rows.
 //
 // grid (16 heads, 8 rows, 2 halves) = 256 blocks of 8 waves, one per CU (every block must be resident: the engine's `chain_resident`
-// gate, bounded sweeps, the error word and the fall-back to the three-launch form are those of the other fused launches, engine.hip).
+// gate, bounded sweeps, the error word and the fall-back to the three-launch form are those of the other fused launches, engine_decode.hpp / engine_generate.hpp).
 // Block (h, b, z):
 //   A. requests, in consumption order: LayerNorm parameters, the vectors of batch row `wave` (the producer's split-K partials + deferred
 //      bias + residual), its 16-row q/k/v weight tile (rows 4 j .. 4 j + 3 of q, k and v of head h, j = 2 b + z: the 16 blocks of a head

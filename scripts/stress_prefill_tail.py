@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Stress of the two-stream prefill (csrc/engine.hip prefill: the rows behind the 256-row tiles as a chain of their own on a second stream).
+"""Stress of the two-stream prefill (csrc/engine_dense.hpp prefill: the rows behind the 256-row tiles as a chain of their own on a second stream).
 Its claim is that NOTHING of the main chain depends on when the tail chain runs, and nothing of the tail chain on anything but the per-layer event: so the
 logits must be the one-stream form's bit for bit whatever the timing.  This script perturbs the timing and compares every run:
   * B = 64, 16 and 40 samples, bf16 and fp16; per case a set of P different prefixes (so that whatever a run leaves in the workspace is NOT what the next

@@ -113,7 +113,8 @@ def test_stale_library_is_detected(lib, tmp_path, monkeypatch):
     import shutil
     from meshanything_amd import build as B
     names = {os.path.basename(f) for f in B.source_files()}
-    assert {"engine.hip", "gemm_decode.hpp", "gemv.hpp", "attn_decode.hpp", "meshanything_amd.h"} <= names
+    assert {"engine.hip", "gemm_decode.hpp", "gemv.hpp", "attn_decode.hpp", "meshanything_amd.h", "engine_state.hpp", "engine_options.hpp", "engine_dense.hpp",
+            "engine_decode.hpp", "engine_generate.hpp", "engine_build.hpp", "engine_experimental.hpp"} <= names
     assert not B.needs_build()                                       # the fixture just loaded a matching library
     csrc = tmp_path / "csrc"
     shutil.copytree(B.CSRC, csrc)

@@ -671,7 +671,7 @@ def test_prefill_kv_written_by_the_qkv_gemm_equals_the_copy(golden_dir, policy):
 def test_prefill_last_rows_as_their_own_chain_equal_the_one_stream_form(golden_dir, policy, B):
     """Round 6: M = B x 257 leaves B rows behind the 256-row tiles -- the last B positions of the last sample, which no other row ever reads (causal
     attention).  With option prefill_tail (default 2: on a stream of the lowest priority; 1: default priority) they run all 24 layers as a chain of their own on a second stream, fed per layer with the main
-    chain's K / V through one event, with the kernels the one-stream form gives them (csrc/engine.hip prefill, gemm256.hpp GemmTArgs::part).  The
+    chain's K / V through one event, with the kernels the one-stream form gives them (csrc/engine_dense.hpp prefill, gemm256.hpp GemmTArgs::part).  The
     logits of the prefill's token and of decode steps that read every cached position -- the last sample's most of all -- must be the one-stream
     form's bit for bit (every stretch of rows gets the kernel the one-stream form gives it: the skinny GEMM behind 256-row tiles, the 128-row tiles in
     the whole problem's shape where that form runs everything on them -- out_proj at 16 / 24 samples), and bit-stable from run to run."""
