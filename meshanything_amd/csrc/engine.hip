@@ -4,9 +4,9 @@
 // Phases (reference: MeshAnything.forward, MeshAnything/models/meshanything.py:134-176):
 //   encode      point cloud -> 257x768 latents -> 257x1024 prefix        (MFMA GEMMs + LDS-tiled attention)
 //   prefill     24 OPT layers over the prefix, fills the KV cache        (same kernels, causal)
-//   decode      <= 7201 steps, each = 123 launches (batch 1: embed + 24 x [qkv | attention | out_proj+merge | fc1 | fc2] + lm_head
+//   decode      <= 7201 steps, each = 51 launches (batch 1: embed + 24 x [q/k/v + attention | out_proj + fc1 + fc2] + lm_head
 //               + pick) replayed from ONE hipGraph per batch size; all step-varying scalars live in per-row device DecState
-//               records, so the graph never changes.  Batches of >= 4 rows (bf16) run the same chain as skinny MFMA GEMMs.
+//               records, so the graph never changes.  Batches of >= 4 rows (bf16) run the layers as skinny MFMA GEMMs.
 //   detokenize  codebook gather + 6 BERT layers over 1057 tokens + per-coordinate argmax
 #include <hip/hip_runtime.h>
 
@@ -266,13 +266,13 @@ int ma_encode(ma_engine* e, const void* pc, int pc_dtype, int B, float* latents,
         if (pc_dtype != MA_DTYPE_F32 && pc_dtype != MA_DTYPE_F16) throw MaError(MA_ERR_INVALID, "pc_dtype must be F32 or F16");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         RoctxRange range("ma_encode");
-        DenseScope enc(e, e->bf16 && !e->enc_exact);
+        const Dense enc{e, s, e->bf16 && !e->enc_exact};
         const size_t pstride = (size_t)e->cfg.n_points * 6 * (pc_dtype == MA_DTYPE_F16 ? 2 : 4);
         for (int b0 = 0; b0 < B; b0 += e->dense_rows) {          // the whole chunk goes through every GEMM at once (M = nb x rows)
             const int nb = std::min(e->dense_rows, B - b0);
             float* lat = latents + (size_t)b0 * e->T * e->cfg.enc_width;
-            encode_chunk(e, s, reinterpret_cast<const char*>(pc) + b0 * pstride, pc_dtype, nb, lat);
-            if (prefix) prefix_chunk(e, s, lat, prefix + (size_t)b0 * e->T * e->cfg.hidden, nb);
+            encode_chunk(enc, reinterpret_cast<const char*>(pc) + b0 * pstride, pc_dtype, nb, lat);
+            if (prefix) prefix_chunk(enc, lat, prefix + (size_t)b0 * e->T * e->cfg.hidden, nb);
         }
     });
 }
@@ -282,11 +282,11 @@ int ma_to_shape_latents(ma_engine* e, const float* latents, int B, float* out, v
     return guarded(e, [&] {
         require_ready(e); check_batch(e, B);
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        DenseScope enc(e, e->bf16 && !e->enc_exact);
+        const Dense enc{e, s, e->bf16 && !e->enc_exact};
         const size_t n = (size_t)e->cfg.num_latents * e->cfg.enc_width;
         for (int b0 = 0; b0 < B; b0 += e->dense_rows) {
             const int nb = std::min(e->dense_rows, B - b0);
-            shape_latents_chunk(e, s, latents + b0 * n, e->cfg.enc_width, RowMap{0, 0, 0}, nb);
+            shape_latents_chunk(enc, latents + b0 * n, e->cfg.enc_width, RowMap{0, 0, 0}, nb);
             HIP_CHECK(hipMemcpyAsync(out + b0 * n, e->w_lat2, (size_t)nb * n * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     });
@@ -297,10 +297,10 @@ int ma_process_point_feature(ma_engine* e, const float* point_feature, int B, fl
     return guarded(e, [&] {
         require_ready(e); check_batch(e, B);
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        DenseScope enc(e, e->bf16 && !e->enc_exact);
+        const Dense enc{e, s, e->bf16 && !e->enc_exact};
         for (int b0 = 0; b0 < B; b0 += e->dense_rows) {
             const int nb = std::min(e->dense_rows, B - b0);
-            prefix_chunk(e, s, point_feature + (size_t)b0 * e->T * e->cfg.enc_width, prefix + (size_t)b0 * e->T * e->cfg.hidden, nb);
+            prefix_chunk(enc, point_feature + (size_t)b0 * e->T * e->cfg.enc_width, prefix + (size_t)b0 * e->T * e->cfg.hidden, nb);
         }
     });
 }
@@ -314,7 +314,7 @@ int ma_get_codes(ma_engine* e, const int64_t* ids, int B, float* codes, void* st
         for (int b0 = 0; b0 < B; b0 += e->dense_rows) {
             const int nb = std::min(e->dense_rows, B - b0);
             hipLaunchKernelGGL((codes_gather2_kernel<float>), dim3(ceil_div(nb * nf * 3 * (D / 4), 256)), dim3(256), 0, s, reinterpret_cast<const long long*>(ids) + (size_t)b0 * nf * 9,
-                               e->PF(DEC + "quantize_codebooks"), D, nb * nf, codes + (size_t)b0 * nf * 3 * D, (float*)nullptr, e->w_mask);
+                               e->dw.codebooks, D, nb * nf, codes + (size_t)b0 * nf * 3 * D, (float*)nullptr, e->w_mask);
             HIP_CHECK(hipGetLastError());
         }
     });
@@ -356,7 +356,7 @@ int ma_detokenize_embeds(ma_engine* e, const int64_t* ids, const float* codes, c
         const size_t nf = e->nf;
         for (int b0 = 0; b0 < B; b0 += e->dense_rows) {
             const int nb = std::min(e->dense_rows, B - b0);
-            detok_chunk(e, s, reinterpret_cast<const long long*>(ids) + (size_t)b0 * nf * 9, codes ? codes + (size_t)b0 * nf * 3 * e->cfg.codebook_dim : nullptr,
+            detok_chunk(Dense{e, s, e->bf16}, reinterpret_cast<const long long*>(ids) + (size_t)b0 * nf * 9, codes ? codes + (size_t)b0 * nf * 3 * e->cfg.codebook_dim : nullptr,
                         latents + (size_t)b0 * e->T * e->cfg.enc_width, coords + (size_t)b0 * nf * 9, nb);
         }
     });

@@ -20,6 +20,37 @@ void validate_config(const ma_config& c) {
     if ((size_t)(c.codebook_size + 3) * 4 + 20 * 1024 > 64 * 1024) bad("codebook_size too large for the sampler's LDS stage (max 11261)");
 }
 
+// every matrix / bias / LayerNorm pair of the dense phases, by its arena name, into e->dw (engine_state.hpp)
+void resolve_dense_weights(ma_engine* e) {
+    const ma_config& c = e->cfg;
+    auto lin = [&](const std::string& p, bool bias = true) {
+        const Entry& en = e->entry(p + ".weight");
+        return Lin{e->arena + en.offset, bias ? e->PF(p + ".bias") : nullptr, en.rows, en.cols, en.dtype, en.name.c_str()};
+    };
+    auto ln = [&](const std::string& p, float eps = 1e-5f) { return LnW{e->PF(p + ".weight"), e->PF(p + ".bias"), eps}; };
+    auto resblock = [&](const std::string& p) { return ResBlockW{ln(p + "ln_1"), ln(p + "ln_2"), lin(p + "attn.c_qkv", false), lin(p + "attn.c_proj"), lin(p + "mlp.c_fc"), lin(p + "mlp.c_proj")}; };
+    DenseW& w = e->dw;
+    w.query = e->PF(SM + "encoder.query"); w.input_proj = lin(SM + "encoder.input_proj");
+    const std::string cp = SM + "encoder.cross_attn.";
+    w.cross = CrossBlockW{ln(cp + "ln_1"), ln(cp + "ln_2"), ln(cp + "ln_3"), lin(cp + "attn.c_q", false), lin(cp + "attn.c_kv", false), lin(cp + "attn.c_proj"), lin(cp + "mlp.c_fc"), lin(cp + "mlp.c_proj")};
+    for (int n = 0; n < c.enc_layers; ++n) w.enc.push_back(resblock(SM + "encoder.self_attn.resblocks." + std::to_string(n) + "."));
+    w.ln_post = ln(SM + "encoder.ln_post"); w.pre_kl = lin(SM + "pre_kl"); w.post_kl = lin(SM + "post_kl");
+    for (int n = 0; n < c.shape_layers; ++n) w.shape.push_back(resblock(SM + "transformer.resblocks." + std::to_string(n) + "."));
+    w.cond_head = lin("cond_head_proj"); w.cond = lin("cond_proj");
+    w.cond_embed = e->PF(DEC + "cond_embed.weight"); w.embed_pos = e->PF(DEC + "embed_positions.weight");
+    for (int l = 0; l < c.layers; ++l) {
+        const std::string p = DEC + "layers." + std::to_string(l) + ".";
+        w.opt.push_back(PostLnLayerW{lin(p + "qkv"), lin(p + "self_attn.out_proj"), lin(p + "fc1"), lin(p + "fc2"), ln(p + "self_attn_layer_norm"), ln(p + "final_layer_norm")});
+    }
+    w.tok_cond_head = lin(TOK + "cond_head_proj"); w.tok_cond = lin(TOK + "cond_proj"); w.project_down = lin(TOK + "project_down_codebook"); w.to_coor = lin(TOK + "to_coor_logits.0");
+    w.point_ln = ln(TOK + "point_layernorm"); w.face_ln = ln(TOK + "layernorm");
+    w.point_pe = e->PF(TOK + "point_pe.weight"); w.pos_emb = e->PF(TOK + "pos_embedding.weight"); w.codebooks = e->PF(DEC + "quantize_codebooks");
+    for (int n = 0; n < c.tok_layers; ++n) {
+        const std::string p = TOK + "decoder.layer." + std::to_string(n) + ".";
+        w.bert.push_back(PostLnLayerW{lin(p + "qkv"), lin(p + "attention.output.dense"), lin(p + "intermediate.dense"), lin(p + "output.dense"), ln(p + "attention.output.LayerNorm", 1e-12f), ln(p + "output.LayerNorm", 1e-12f)});
+    }
+}
+
 void build_engine(ma_engine* e) {
     const ma_config& c = e->cfg;
     e->L = build_layout(c);
@@ -98,8 +129,6 @@ void build_engine(ma_engine* e) {
     // dense workspace: R = dense_rows samples stacked along the rows (R x 4096 point rows / R x 257 latent rows / R x 1057
     // detokenizer rows per pass)
     const int N = c.n_points, W = c.enc_width, T = e->T, Wt = c.tok_width, S = e->S, NL = c.num_latents;
-    e->act_elem = e->bf16 ? 2 : 4;
-    e->dense16 = e->bf16;
     e->enc_exact = !e->bf16 || c.enc_exact != 0;
     const size_t enc_elem = e->enc_exact ? 4 : 2;                    // element size of the buffers the encoder's activations live in
     e->dense_rows = std::min(c.max_batch, 64);                        // 64 x 4096 point rows per pass: 5 GB of workspace at the 350M shape (bf16 policy)
@@ -108,7 +137,7 @@ void build_engine(ma_engine* e) {
     const size_t rows_seq = R * std::max(T, S);                      // rows of the latent / token streams
     const size_t wmax = std::max(W, Wt);
     const size_t fmax = std::max(4 * W, c.tok_ffn);
-    auto amalloc = [&](size_t elems) -> void* { return e->dmalloc<char>(elems * std::max(e->act_elem, enc_elem)); };      // (buffers shared by the phases take the wider element)
+    auto amalloc = [&](size_t elems) -> void* { return e->dmalloc<char>(elems * std::max<size_t>(e->bf16 ? 2 : 4, enc_elem)); };      // (buffers shared by the phases take the wider element)
     e->w_data = e->dmalloc<float>(R * N * W);
     e->w_lat = e->dmalloc<float>(R * T * W); e->w_lat2 = e->dmalloc<float>(R * NL * W);
     e->w_pf = e->dmalloc<float>(R * T * Wt); e->w_x = e->dmalloc<float>(R * S * Wt); e->w_y = e->dmalloc<float>(R * S * Wt);
@@ -140,17 +169,12 @@ void build_engine(ma_engine* e) {
     const size_t B = c.max_batch;
     e->w_latents = e->dmalloc<float>(B * T * W); e->w_prefix = e->dmalloc<float>(B * T * H);
     e->w_tokens = e->dmalloc<long long>(B * e->maxnew); e->w_ids = e->dmalloc<long long>(B * (size_t)e->nf * 9);
-    // per-layer decode pointers
+    resolve_dense_weights(e);
+    // per-layer decode pointers: the matrices the prefill runs, as the decode kernels take them
     e->dl.resize(c.layers);
     for (int l = 0; l < c.layers; ++l) {
-        const std::string p = DEC + "layers." + std::to_string(l) + ".";
-        DecLayerPtrs& w = e->dl[l];
-        w.qkv_w = e->P(p + "qkv.weight"); w.qkv_b = e->PF(p + "qkv.bias");
-        w.o_w = e->P(p + "self_attn.out_proj.weight"); w.o_b = e->PF(p + "self_attn.out_proj.bias");
-        w.fc1_w = e->P(p + "fc1.weight"); w.fc1_b = e->PF(p + "fc1.bias");
-        w.fc2_w = e->P(p + "fc2.weight"); w.fc2_b = e->PF(p + "fc2.bias");
-        w.ln1_g = e->PF(p + "self_attn_layer_norm.weight"); w.ln1_b = e->PF(p + "self_attn_layer_norm.bias");
-        w.ln2_g = e->PF(p + "final_layer_norm.weight"); w.ln2_b = e->PF(p + "final_layer_norm.bias");
+        const PostLnLayerW& w = e->dw.opt[l];
+        e->dl[l] = DecLayerPtrs{w.qkv.w, w.o.w, w.fc1.w, w.fc2.w, w.qkv.b, w.o.b, w.fc1.b, w.fc2.b, w.ln1.g, w.ln1.b, w.ln2.g, w.ln2.b};
     }
     exp_upload_layers(e);
 }

@@ -74,7 +74,7 @@ int generate_batch_once(ma_engine* e, hipStream_t s, const float* prefix, int B,
         RoctxRange range("ma_generate: prefill");
         for (int b0 = 0; b0 < B; b0 += e->prefill_rows) {
             const int nb = std::min(e->prefill_rows, B - b0);
-            prefill(e, s, prefix + (size_t)b0 * e->T * e->cfg.hidden, b0, nb);
+            prefill(Dense{e, s, e->bf16}, prefix + (size_t)b0 * e->T * e->cfg.hidden, b0, nb);
         }
     }
     RoctxRange range_decode("ma_generate: decode steps");

@@ -78,6 +78,20 @@ struct RoctxRange {
 
 }  // namespace
 
+// ---- the dense phases' weights, resolved from the layout once (build_engine: a name the layout does not have fails engine creation);
+// the hot path builds no names and looks nothing up
+struct Lin { const void* w; const float* b; int rows, cols, dtype; const char* name; };      // nn.Linear: weight (rows, cols) of `dtype`, fp32 bias or null; name = the weight's arena entry (error messages)
+struct LnW { const float *g, *b; float eps; };                                                // nn.LayerNorm
+struct ResBlockW { LnW ln1, ln2; Lin qkv, proj, fc, fc_proj; };                               // ResidualAttentionBlock (transformer_blocks.py:109-112)
+struct CrossBlockW { LnW ln1, ln2, ln3; Lin q, kv, proj, fc, fc_proj; };                      // ResidualCrossAttentionBlock (transformer_blocks.py:223-226)
+struct PostLnLayerW { Lin qkv, o, fc1, fc2; LnW ln1, ln2; };                                  // a post-LN layer, q|k|v fused: OPTDecoderLayer, BertLayer
+struct DenseW {
+    const float* query; Lin input_proj; CrossBlockW cross; std::vector<ResBlockW> enc; LnW ln_post;          // point encoder
+    Lin pre_kl, post_kl; std::vector<ResBlockW> shape; Lin cond_head, cond;                                   // shape latents, prefix
+    const float *cond_embed, *embed_pos; std::vector<PostLnLayerW> opt;                                       // prefill
+    Lin tok_cond_head, tok_cond, project_down, to_coor; LnW point_ln, face_ln; const float *point_pe, *pos_emb, *codebooks; std::vector<PostLnLayerW> bert;      // detokenizer
+};
+
 struct ma_engine {
     ma_config cfg{};
     int device = 0;
@@ -178,14 +192,12 @@ struct ma_engine {
     unsigned* d_chain_err = nullptr; unsigned* h_chain_err = nullptr;               // error word + counters of all of them (build_engine)
 
     // ---- dense-phase workspace: dense_rows samples stacked along the rows.  w_* / p_*: fp32 streams; a_*: activation tensors
-    // (dense_ops.hpp: act_elem = 2 bytes under the bf16 policy, 4 under the exact policy)
-    // precision of the dense phase being enqueued (DenseScope): MA_DTYPE_F32 or the engine's 16-bit type.  The point encoder
-    // (ma_encode: encode_latents + process_point_feature, and the detokenizer's projection of the latents) runs in fp32 under a 16-bit
-    // policy when cfg.enc_exact is set -- the north star's 1e-5 on encoder activations in the benchmarked mode; prefill and the
-    // detokenizer's BERT stack follow the policy dtype.
-    bool dense16 = true;
+    // (dense_ops.hpp: 2-byte elements in a 16-bit phase, 4 in an exact one; every phase entry says which in its Dense context, engine_dense.hpp).
+    // The point encoder (ma_encode: encode_latents + process_point_feature, and the detokenizer's projection of the latents) runs in fp32
+    // under a 16-bit policy when cfg.enc_exact is set -- the north star's 1e-5 on encoder activations in the benchmarked mode; prefill and
+    // the detokenizer's BERT stack follow the policy dtype.
     bool enc_exact = false;          // encoder weights are fp32 arena entries and the encoder's activations fp32 (always true under the fp32 policy)
-    size_t act_elem = 2;
+    DenseW dw;                       // the dense phases' weights
     float *w_data = nullptr, *w_lat = nullptr, *w_lat2 = nullptr, *w_pf = nullptr, *w_x = nullptr, *w_y = nullptr, *w_fe = nullptr, *w_logit = nullptr;
     float *p_h = nullptr, *p_y = nullptr;
     long p_y_part_stride = 0;        // p_y holds up to 4 partial sums of a GEMM split along K (gemm256.hpp GemmSplitK), this many floats apart, for the small prefills that use it
@@ -217,11 +229,12 @@ struct ma_engine {
         allocs.push_back(p);
         return reinterpret_cast<Tp*>(p);
     }
-    const void* P(const std::string& name) const {
+    const Entry& entry(const std::string& name) const {
         auto it = L.entry_by_name.find(name);
         if (it == L.entry_by_name.end()) throw MaError(MA_ERR_INVALID, "internal: no arena entry " + name);
-        return arena + L.entries[it->second].offset;
+        return L.entries[it->second];
     }
+    const void* P(const std::string& name) const { return arena + entry(name).offset; }
     const float* PF(const std::string& name) const { return reinterpret_cast<const float*>(P(name)); }
     char* kplane(int row, int layer) const { return kv + (size_t)row * kv_row_bytes + (size_t)(2 * layer) * kv_plane; }
     char* vplane(int row, int layer) const { return kv + (size_t)row * kv_row_bytes + (size_t)(2 * layer + 1) * kv_plane; }

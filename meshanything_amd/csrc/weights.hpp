@@ -74,7 +74,7 @@ inline Layout build_layout(const ma_config& c) {
     Layout L;
     const int mdt = c.dtype == MA_DTYPE_F32 ? MA_DTYPE_F32 : (c.dtype == MA_DTYPE_F16 ? MA_DTYPE_F16 : MA_DTYPE_BF16);
     // the point encoder's matrices (and the two projections of its latents in front of the decoder and of the detokenizer): fp32 when
-    // cfg.enc_exact asks for the exact encoder under a 16-bit policy (engine_dense.hpp, DenseScope)
+    // cfg.enc_exact asks for the exact encoder under a 16-bit policy (engine_dense.hpp: the encoder phases' Dense context)
     const int edt = (c.dtype == MA_DTYPE_F32 || c.enc_exact) ? MA_DTYPE_F32 : mdt;
     const int W = c.enc_width, T = c.num_latents + 1, H = c.hidden, E = c.embed_dim;
     const int fourier = 3 * (2 * c.num_freqs + 1), pin = fourier + 3;
