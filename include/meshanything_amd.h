@@ -306,6 +306,11 @@ MA_API int  ma_engine_persist_available(ma_engine *e);
 MA_API int  ma_persist_trace(ma_engine *e, int kv_len, uint64_t *host_out, int32_t *n_events, void *stream);
 /* copies the logits of the most recent decode step of batch row `row` (codebook_size + 3 floats) into a device buffer */
 MA_API int  ma_engine_read_logits(ma_engine *e, int row, float *out, void *stream);
+/* test aid for the decode step's embedding table (engine option "embed_table": row v = input_layer(codebook[v]) + bias, built once per set of
+ * weights; the token pick writes the next step's layer-0 input from it, so that the step has no embedding launch).  Writes n rows of `hidden` floats
+ * to `out` (device).  what 0: table rows row0 .. row0 + n - 1.  what 1: the embedding launch's own value for the tokens row0 + 3 .. row0 + n + 2 in
+ * front of its positional adds (uses batch row 0's state record). */
+MA_API int  ma_engine_embed_rows(ma_engine *e, int what, int row0, int n, float *out, void *stream);
 
 /* ---- watertight remeshing of a mesh input (csrc/watertight.hpp).  replaces: export_to_watertight (mesh_to_pc.py:13-40), i.e.
  * mesh2sdf.core.compute + skimage.measure.marching_cubes(np.abs(sdf), level).  Needs no engine; errors via ma_last_error(NULL).

@@ -96,6 +96,7 @@ SIGNATURES = {
     "ma_engine_persist_available": (_I, [_P]),
     "ma_persist_trace": (_I, [_P, _I, _P, C.POINTER(C.c_int32), _P]),
     "ma_engine_read_logits": (_I, [_P, _I, _P, _P]),
+    "ma_engine_embed_rows": (_I, [_P, _I, _I, _I, _P, _P]),
     "ma_op_mesh_udf": (_I, [_P, _I, _P, _I, _I, _P, _P, C.c_size_t, _P]),
     "ma_mesh_udf_workspace_bytes": (C.c_size_t, [_I]),
     "ma_op_marching_cubes": (_I, [_P, _I, _I, _I, _F, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_size_t, _P]),

@@ -609,7 +609,7 @@ int ma_profile_decode(ma_engine* e, int kv_len, int steps, ma_kernel_timing* out
         std::memset(out, 0, sizeof(*out));
         const int B = std::max(1, std::min(e->opt.profile_batch, e->cfg.max_batch));
         const int impl = persist_selected(e, B, 0) ? 1 : 0;
-        if (impl == 1) ensure_embtab(e, s);
+        if (impl == 1 || embed_from_table(e, B)) ensure_embtab(e, s);
         ensure_graphs(e, B, impl);
         auto reset = [&] { state_at(e, s, B, kv_len); };
         hipEvent_t a, b;
@@ -665,7 +665,8 @@ int ma_trace_decode(ma_engine* e, int kv_len, uint64_t* host_out, int max_launch
         if (kv_len < e->T + 1 || kv_len + 16 > e->maxseq) throw MaError(MA_ERR_INVALID, "kv_len out of range");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         const int TB = std::max(1, std::min(e->opt.profile_batch, e->cfg.max_batch));      // rows of the traced step (option profile_batch)
-        state_at(e, s, TB, kv_len);
+        if (embed_from_table(e, TB)) ensure_embtab(e, s);
+        state_at(e, s, TB, kv_len);      // (embed_table: includes the one embedding launch that feeds the first step; trace kind 0 then has no slot)
         const size_t n64 = (size_t)max_launches * max_blocks * 4;
         unsigned long long* d_tr = nullptr;
         HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_tr), n64 * sizeof(unsigned long long)));
@@ -700,6 +701,42 @@ int ma_engine_read_logits(ma_engine* e, int row, float* out, void* stream) {
     return guarded(e, [&] {
         if (row < 0 || row >= e->cfg.max_batch) throw MaError(MA_ERR_INVALID, "row out of range");
         HIP_CHECK(hipMemcpyAsync(out, e->d_logits + (size_t)row * e->V, (size_t)e->V * sizeof(float), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// test aid (tests/test_gpu_embed_table.py): `n` rows of hidden floats into the caller's device buffer.
+// what 0: rows [row0, row0 + n) of the embedding table (built first when the weights changed since).
+// what 1: what the step's embedding launch (gemv_kernel, EPI_EMBED) computes for the tokens row0 + 3 .. row0 + n + 2 in front of its positional adds: the
+//         launch itself, one token at a time through batch row 0's state record, with all-zero tables in place of the three positional ones.
+int ma_engine_embed_rows(ma_engine* e, int what, int row0, int n, float* out, void* stream) {
+    if (!e || !out) return MA_ERR_INVALID;
+    return guarded(e, [&] {
+        require_ready(e);
+        const ma_config& c = e->cfg;
+        if ((what != 0 && what != 1) || row0 < 0 || n < 1 || row0 > c.codebook_size - n) throw MaError(MA_ERR_INVALID, "ma_engine_embed_rows: what must be 0 or 1, the rows inside [0, codebook_size)");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        const size_t H = c.hidden;
+        if (what == 0) {
+            ensure_embtab(e, s);
+            HIP_CHECK(hipMemcpyAsync(out, e->d_embtab + (size_t)row0 * H, (size_t)n * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return;
+        }
+        // step 0 reads slot row 10 of token_embed_positions, row 1 of cond_embed and row T + 1 of embed_positions
+        const size_t zrows = (size_t)std::max(e->T + 2, 12);
+        float* z = nullptr;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&z), zrows * H * sizeof(float)));
+        try {
+            HIP_CHECK(hipMemsetAsync(z, 0, zrows * H * sizeof(float), s));
+            for (int i = 0; i < n; ++i) {
+                hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(64), 0, s, e->d_st, 0, e->T - 1, row0 + i + 3, 1);
+                HIP_CHECK(hipGetLastError());
+                GemvArgs a = make_embed_args(e, Rows{0, 1});
+                a.tokpos = z; a.cond = z; a.postab = z; a.y = out + (size_t)i * H;
+                gemv(e, a, s, 1);
+            }
+            HIP_CHECK(hipStreamSynchronize(s));
+        } catch (...) { (void)hipFree(z); throw; }
+        HIP_CHECK(hipFree(z));
     });
 }
 

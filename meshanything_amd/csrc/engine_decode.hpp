@@ -368,6 +368,33 @@ void enqueue_layer(ma_engine* e, hipStream_t s, int l, const float* x_in, const 
 }
 
 
+// ---- embedding table (option embed_table): row v = input_layer(codebook[v]) + bias for every codebook row, (V - 3) x hidden fp32 (33.5 MB at the
+// 350M shape).  The value depends on the token and on weights that do not change after load_weights, so the step does not stream the 2.1 MB
+// input_layer matrix for it again: pick_kernel<true> reads the chosen token's row and writes the next step's layer-0 input (misc.hpp).
+// Built by the step's own GEMV: ONE launch of the gemv_kernel instantiation the embedding launch uses (same shape, same rounding of the
+// input, same order of every sum), with the codebook rows as its batch rows, so that a row holds the bits `v + e_bias` has in that launch's
+// EPI_EMBED epilogue (tests/test_gpu_embed_table.py compares them).  Built lazily by the first generation / profile / trace after the weights
+// changed (every loader clears embtab_ready; so do the setters that change that GEMV's shape: CLEARS_EMBTAB, engine_options.hpp); the
+// experimental persistent step reads the same table.
+void ensure_embtab(ma_engine* e, hipStream_t s) {
+    if (e->embtab_ready && e->embtab_small_rows == gemv_small_rows()) return;      // (gemv_small_rows is process-wide: another engine may have set it)
+    const ma_config& c = e->cfg;
+    const int rows_per_launch = 32768;                                             // grid.y
+    for (int v0 = 0; v0 < c.codebook_size; v0 += rows_per_launch) {
+        GemvArgs a{};
+        a.round_x = e->bf16 ? 1 : 0; a.act = ACT_NONE; a.epi = EPI_PLAIN;
+        a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias");
+        a.x = e->PF(DEC + "quantize_codebooks") + (size_t)v0 * c.codebook_dim; a.x_stride = c.codebook_dim;
+        a.y = e->d_embtab + (size_t)v0 * c.hidden; a.y_stride = c.hidden; a.N = c.hidden; a.K = c.codebook_dim;
+        gemv(e, a, s, std::min(rows_per_launch, c.codebook_size - v0));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    e->embtab_ready = true; e->embtab_small_rows = gemv_small_rows();
+}
+// Where the step's embedding is gemv_kernel<..., EPI_EMBED> alone: the GEMV chain (batch 1 fused or five launches, rows in the grid) in every policy.
+// The matrix-core batches keep the launch: it also leaves the 16-bit operand of layer 0's q/k/v GEMM, and a launch is <= 0.6 % of their step.
+bool embed_from_table(ma_engine* e, int B) { return e->opt.embed_table && !use_mfma_decode(e, B) && e->cfg.hidden % 4 == 0; }
+
 // the measured-and-rejected step forms: their host side, or -- the product build -- the stubs that say "never"
 #ifdef MA_EXPERIMENTAL
 }  // namespace
@@ -377,7 +404,6 @@ namespace {
 bool use_rows_fused(ma_engine*, int, int) { return false; }
 bool fuse_layer(ma_engine*, int = 1, int = -1) { return false; }
 bool persist_selected(ma_engine*, int, int) { return false; }
-void ensure_embtab(ma_engine*, hipStream_t) {}
 void check_persist_error(ma_engine*, hipStream_t) {}
 void exp_reset_exchanges(ma_engine*, hipStream_t) {}
 void exp_alloc_exchanges(ma_engine*) {}
@@ -398,9 +424,23 @@ void enqueue_lm_head(ma_engine* e, hipStream_t s, const float* x, int x_stride, 
 
 void enqueue_pick(ma_engine* e, hipStream_t s, StepTimer& tm, Rows rw) {
     if (!tm.on(3)) return;
-    hipLaunchKernelGGL(pick_kernel, dim3(rw.B), dim3(256), (size_t)e->V * sizeof(float), s, e->d_logits + (size_t)rw.r0 * e->V, e->V,
-                       e->d_pval + (size_t)rw.r0 * e->V, e->d_pidx + (size_t)rw.r0 * e->V, (use_mfma_decode(e, rw.B) && !use_rows_fused(e, rw.B, -1)) ? 0 : e->n_parts, e->V, e->d_st + rw.r0,
-                       e->w_tokens + (size_t)rw.r0 * e->maxnew, e->maxnew, e->T);
+    const int nparts = (use_mfma_decode(e, rw.B) && !use_rows_fused(e, rw.B, -1)) ? 0 : e->n_parts;
+    PickEmbed em{};
+    const bool emb = embed_from_table(e, rw.B);
+    if (emb) {
+        // (a captured step cannot build the table: generate / profile / trace call ensure_embtab before they capture or enqueue)
+        if (!e->embtab_ready) throw MaError(MA_ERR_STATE, "internal: decode step enqueued before the embedding table was built");
+        const int H = e->cfg.hidden;
+        em.table = e->d_embtab; em.extra = e->PF(DEC + "extra_embeds.weight"); em.tokpos = e->PF(DEC + "token_embed_positions.weight");
+        em.cond = e->PF(DEC + "cond_embed.weight"); em.postab = e->PF(DEC + "embed_positions.weight"); em.pos_rows = e->entry(DEC + "embed_positions.weight").rows;
+        em.e_out = e->d_e + (size_t)rw.r0 * H; em.e_stride = H; em.H = H;
+    }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(rw.B), dim3(256), (size_t)e->V * sizeof(float), s, e->d_logits + (size_t)rw.r0 * e->V, e->V,
+                           e->d_pval + (size_t)rw.r0 * e->V, e->d_pidx + (size_t)rw.r0 * e->V, nparts, e->V, e->d_st + rw.r0,
+                           e->w_tokens + (size_t)rw.r0 * e->maxnew, e->maxnew, e->T, em);
+    };
+    if (emb) launch(pick_kernel<true>); else launch(pick_kernel<false>);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -415,6 +455,26 @@ void check_chain_error(ma_engine* e, hipStream_t s) {
     }
 }
 
+// The embedding launch: e = (extra[tok] | input_layer(codebook[tok - 3]) + bias) + the three positional rows, for the token and step in DecState.
+// The first launch of every step without embed_table; with it, only behind a state that no pick produced (state_at, engine_generate.hpp).
+GemvArgs make_embed_args(ma_engine* e, Rows rw) {
+    const ma_config& c = e->cfg;
+    const int H = c.hidden;
+    GemvArgs a = gemv_base(e, rw);
+    a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias"); a.y = e->d_e + (size_t)rw.r0 * H; a.y_stride = H; a.N = H; a.K = c.codebook_dim;
+    a.epi = EPI_EMBED; a.codebook = e->PF(DEC + "quantize_codebooks"); a.extra = e->PF(DEC + "extra_embeds.weight");
+    a.tokpos = e->PF(DEC + "token_embed_positions.weight"); a.cond = e->PF(DEC + "cond_embed.weight");
+    a.postab = e->PF(DEC + "embed_positions.weight"); a.T = e->T;
+    // batched matrix-core step: the embedding launch also leaves the 16-bit operand of layer 0's q/k/v GEMM (no prologue launch for it)
+    if (use_mfma_decode(e, rw.B)) { a.yb = e->d_xb + (size_t)rw.r0 * H; a.yb_stride = H; }
+    return a;
+}
+void enqueue_embed(ma_engine* e, hipStream_t s, StepTimer& tm, Rows rw) {
+    GemvArgs a = make_embed_args(e, rw);
+    a.trace = tm.trace_slot(0, gemv_blocks(e, a.N, a.K));
+    if (tm.on(0)) gemv(e, a, s, rw.B);
+}
+
 // One full decode step (shape_opt.py:318-328 embedding branch -> 24 layers -> lm_head -> pick) for rows r0..r0+B-1.
 // Replayable: no host-side step-dependent argument.
 void enqueue_decode_step(ma_engine* e, hipStream_t s, int len_override, StepTimer& tm, Rows rw = Rows{}, int impl = 0) {
@@ -426,17 +486,8 @@ void enqueue_decode_step(ma_engine* e, hipStream_t s, int len_override, StepTime
     const ma_config& c = e->cfg;
     const int H = c.hidden;
     float* de = e->d_e + (size_t)rw.r0 * H;
-    {
-        GemvArgs a = gemv_base(e, rw);
-        a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias"); a.y = de; a.y_stride = H; a.N = H; a.K = c.codebook_dim;
-        a.epi = EPI_EMBED; a.codebook = e->PF(DEC + "quantize_codebooks"); a.extra = e->PF(DEC + "extra_embeds.weight");
-        a.tokpos = e->PF(DEC + "token_embed_positions.weight"); a.cond = e->PF(DEC + "cond_embed.weight");
-        a.postab = e->PF(DEC + "embed_positions.weight"); a.T = e->T;
-        // batched matrix-core step: the embedding launch also leaves the 16-bit operand of layer 0's q/k/v GEMM (no prologue launch for it)
-        if (use_mfma_decode(e, rw.B)) { a.yb = e->d_xb + (size_t)rw.r0 * H; a.yb_stride = H; }
-        a.trace = tm.trace_slot(0, gemv_blocks(e, a.N, a.K));
-        if (tm.on(0)) gemv(e, a, s, rw.B);
-    }
+    // embed_table: the previous pick (or enqueue_embed behind a state set by hand) left this step's layer-0 input in `de`
+    if (!embed_from_table(e, rw.B)) enqueue_embed(e, s, tm, rw);
 #ifdef MA_EXPERIMENTAL
     if (use_rows_fused(e, rw.B, len_override)) {
         const float* y2 = e->d_ypre2 + (size_t)rw.r0 * H;

@@ -53,6 +53,9 @@ void state_at(ma_engine* e, hipStream_t s, int B, int kv_len) {
     init_state(e, s, sc, B, e->maxnew);
     hipLaunchKernelGGL(set_pos_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, e->d_st, kv_len - e->T, kv_len - 1, 5, B);
     HIP_CHECK(hipGetLastError());
+    // embed_table: no pick produced this state, so nothing wrote the layer-0 input of the step that follows: one embedding launch does
+    // (ma_profile_decode, ma_trace_decode, ma_persist_trace all come through here; generate()'s first step is fed by the pick after the prefill)
+    if (embed_from_table(e, B)) { StepTimer none; enqueue_embed(e, s, none, Rows{0, B}); }
 }
 
 // generate() for a batch of B rows: every row is prefilled, then all rows step together (they share the weight stream and
@@ -66,7 +69,7 @@ int generate_batch_once(ma_engine* e, hipStream_t s, const float* prefix, int B,
     // (the persistent step carries its own pick: teacher forcing / logits capture take the launch chain)
     const bool parity_aid = sc.forced_tokens || sc.logits_out;
     const int impl = (persist_selected(e, B, sc.do_sample) && !parity_aid) ? 1 : 0;
-    if (impl == 1) ensure_embtab(e, s);
+    if (impl == 1 || embed_from_table(e, B)) ensure_embtab(e, s);
     ensure_graphs(e, B, impl);
     init_state(e, s, sc, B, maxn);
     // prefill in groups of rows (bounded workspace: prefill_rows samples at a time)
@@ -80,7 +83,8 @@ int generate_batch_once(ma_engine* e, hipStream_t s, const float* prefix, int B,
     RoctxRange range_decode("ma_generate: decode steps");
     if (e->opt.prefill_stepwise) init_state(e, s, sc, B, maxn);         // the stepwise prefill used the state's pos field
     StepTimer none;
-    enqueue_pick(e, s, none, Rows{0, B});                                // token 0 (expected bos; dropped later, meshanything.py:166)
+    // token 0 (expected bos; dropped later, meshanything.py:166); embed_table: this pick also writes the first decode step's layer-0 input
+    enqueue_pick(e, s, none, Rows{0, B});
     int produced = 1;
     bool finished = false;
     while (produced < maxn && !finished) {

@@ -81,6 +81,9 @@ const Opt OPTIONS[] = {
     {.name = "fuse_fc2", .field = &Options::fuse_fc2, .effects = DROPS_GRAPHS},
     {.name = "qkv_xcd_local", .field = &Options::qkv_xcd_local, .flag = true, .effects = DROPS_GRAPHS},
     {.name = "oproj_fc1_sweep_waves", .field = &Options::oproj_fc1_sweep_waves, .effects = DROPS_GRAPHS},
+    // (read back as the engine will apply it at profile_batch rows: the matrix-core batches keep their embedding launch)
+    {.name = "embed_table", .field = &Options::embed_table, .get = [](ma_engine* e) -> int64_t { return embed_from_table(e, std::max(1, std::min(e->opt.profile_batch, e->cfg.max_batch))) ? 1 : 0; },
+     .flag = true, .effects = DROPS_GRAPHS},
     {.name = "fuse_layer", .field = &Options::fuse_layer, .get = [](ma_engine* e) -> int64_t { return fuse_layer(e) ? 1 : 0; }, .product = zero_only, .needs_exp = "fuse_layer" MA_NEEDS_EXP, .effects = DROPS_GRAPHS},
     // ---- decode step, matrix-core chain (mfma_chunks is process-wide: gemm_decode.hpp)
     {.name = "mfma_min_batch", .field = &Options::mfma_min_batch, .effects = DROPS_GRAPHS},

@@ -144,6 +144,7 @@ struct ma_engine {
         int rows_attn_early = 6;         // rows_attn.hpp: when the first cache rounds are requested (A/B, see the kernel): 5 = the q/k/v sweep by scalar loads (waves 0 .. 3), two rounds by the waves 4 .. 7 meanwhile; 6 = 5 + rounds wholly below the newest position run without masks; 3 = one round behind the q/k/v MFMAs, sweep by vector loads
         int rows_mlp_prefetch = 0;       // rows_mlp.hpp step F (measured, not kept: 0 = off): the next layer's first operands pulled into L2 by the blocks that idle during step E -- 1 | 2 rounds, 8 = weights only, 9 = half a round
         int rows_mlp_ln2 = 1;            // rows_mlp.hpp step E: LayerNorm 2 finished in the MLP launch (the next q/k/v starts from 16-bit rows)
+        int embed_table = 1;             // GEMV chain: the pick writes the next step's layer-0 input from the load-time table (misc.hpp pick_kernel<true>); 0: an embedding launch per step
         int gemm_xcd_swizzle = 1;        // dense GEMM: hand the tiles out XCD-aware (gemm_tile.hpp)
         int attn_impl = 2;               // bf16 dense attention: 2 = swapped-operand 32x32x16 kernel on packed V^T (attn2.hpp), 1 = attention_mfma_kernel (attn.hpp)
         int qkv_to_cache = 1;            // prefill (16-bit policies): the q|k|v GEMM writes K / V into the cache planes itself where it can (gemm256.hpp KV form); 0: always by kv_fill_rows_kernel (A/B)
@@ -172,11 +173,12 @@ struct ma_engine {
     bf16_t *d_xb = nullptr, *d_ffb = nullptr;      // bf16 activations of the batched path: [max_batch][hidden], [max_batch][ffn]
     float *d_ks_o = nullptr, *d_ks_f = nullptr;    // split-K partials of out_proj / fc2: [4][max_batch][hidden]
     unsigned* d_pf_sink = nullptr;                 // (rows_mlp_prefetch)
+    // embedding table (option embed_table; engine_decode.hpp ensure_embtab): read by the pick, and by the experimental persistent step
+    float* d_embtab = nullptr;       // [codebook_size][hidden] fp32: input_layer(codebook row) + bias, built by the chain's own GEMV
+    bool embtab_ready = false; int embtab_small_rows = -1;      // ... for the weights in the arena, with this gemv_small_rows
     // the persistent step's (MA_EXPERIMENTAL)
-    bool embtab_ready = false;
     DecLayerPtrs* d_layers = nullptr;
     u64* d_gran = nullptr; unsigned* d_serial = nullptr; unsigned* d_err = nullptr; unsigned* h_err = nullptr;
-    float* d_embtab = nullptr;       // [codebook_size][hidden] fp32: input_layer(codebook row) + bias, built by the chain's own GEMV
     u64* d_ptrace = nullptr;
 
     // ---- exchange buffers of the launches that hand data over inside a launch (granules: common.hpp)

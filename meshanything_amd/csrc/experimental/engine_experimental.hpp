@@ -55,24 +55,6 @@ void enqueue_layer_pair(ma_engine* e, hipStream_t s, int l, const float* resid, 
 bool persist_eligible(ma_engine* e, int B, int do_sample) { return e->persist_shape && B == 1 && !do_sample; }
 bool persist_selected(ma_engine* e, int B, int do_sample) { return e->opt.decode_impl == 1 && persist_eligible(e, B, do_sample); }
 
-// embedding table of the persistent step: row v = input_layer(codebook[v]) + bias, computed by the launch chain's own GEMV
-// (same kernel, same rounding points: the table holds exactly the bits the chain's embedding launch produces for token v + 3)
-void ensure_embtab(ma_engine* e, hipStream_t s) {
-    if (e->embtab_ready) return;
-    const ma_config& c = e->cfg;
-    const float* cb = e->PF(DEC + "quantize_codebooks");
-    for (int v = 0; v < c.codebook_size; ++v) {
-        GemvArgs a{};
-        a.round_x = 1; a.act = ACT_NONE; a.epi = EPI_PLAIN;
-        a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias"); a.x = cb + (size_t)v * c.codebook_dim;
-        a.y = e->d_embtab + (size_t)v * c.hidden; a.N = c.hidden; a.K = c.codebook_dim;
-        const hipError_t r = launch_gemv<bf16_t>(a, s, 1);
-        if (r != hipSuccess) throw MaError(MA_ERR_HIP, std::string("embedding table gemv failed: ") + hipGetErrorString(r));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    e->embtab_ready = true;
-}
-
 void enqueue_persist_step(ma_engine* e, hipStream_t s, StepTimer& tm, u64* trace = nullptr) {
     if (!tm.on(2)) return;
     const ma_config& c = e->cfg;
@@ -128,7 +110,6 @@ void exp_build_gates(ma_engine* e, const hipDeviceProp_t& prop) {
     if (!e->persist_shape) return;
     e->d_layers = e->dmalloc<DecLayerPtrs>(c.layers);
     e->d_gran = e->dmalloc<u64>(PG_TOTAL); e->d_serial = e->dmalloc<unsigned>(1); e->d_err = e->dmalloc<unsigned>(1);
-    e->d_embtab = e->dmalloc<float>((size_t)c.codebook_size * c.hidden);
     e->d_ptrace = e->dmalloc<u64>((size_t)PS_CUS * (PS_TRACE_EVENTS + PS_TRACE2_EVENTS));
     HIP_CHECK(hipMemset(e->d_gran, 0, PG_TOTAL * sizeof(u64)));
     const unsigned one = 1u;

@@ -56,10 +56,22 @@ __device__ inline float hash_uniform(unsigned long long seed, int row, int t) {
 
 constexpr int PICK_KMAX = 64;
 
+// EMB (engine option embed_table): the pick also writes the NEXT step's layer-0 input, so that the step needs no embedding launch
+// (gemv_kernel EPI_EMBED: a 2.1 MB matrix streamed per step for a value that depends on the token only).  `table` row v holds
+// input_layer(codebook[v]) + bias as that launch computes it (ensure_embtab builds it with the same gemv_kernel instantiation), and the
+// adds below run in the epilogue's order, so e_out holds the bits the launch would have written.
+struct PickEmbed {
+    const float* table;                                  // [V - 3][H]
+    const float *extra, *tokpos, *cond, *postab;         // extra_embeds, token_embed_positions, cond_embed, embed_positions ([pos_rows][H])
+    float* e_out; int e_stride;                          // row b of the launch writes e_out + b * e_stride
+    int H, pos_rows;                                     // H % 4 == 0
+};
+
 // grid = batch rows: block b owns row b's logits, partials, state record and output row (nothing is shared between blocks).
+template <bool EMB>
 __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ logits, int V, const float* __restrict__ part_val,
                                                    const int* __restrict__ part_idx, int nparts, int part_stride, DecState* st,
-                                                   long long* __restrict__ tokens_out, int tokens_stride, int T) {
+                                                   long long* __restrict__ tokens_out, int tokens_stride, int T, PickEmbed em) {
     logits += (size_t)blockIdx.x * V;
     part_val += (size_t)blockIdx.x * part_stride;
     part_idx += (size_t)blockIdx.x * part_stride;
@@ -83,6 +95,19 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
     for (int j = 0; j < PICK_PRE; ++j) pre[j] = logits[preloaded ? min(tid + 256 * j, V - 1) : 0];
     const DecState sv = *st;
     const int do_sample = sv.do_sample;
+    // EMB: the three operands of the next step's embedding that depend on t only are requested here, in front of the argmax / sampler
+    // (clamped indices, no lane-dependent guard around a load); only the table / extra row waits for the token.  The next step's
+    // launch would have read t' = t + 1: slot (t' - 2) mod 9 + 3 (python modulo), position row T + t' - 1 + 2.
+    const int c0 = EMB ? min(tid * 4, em.H - 4) : 0;
+    f32x4 p_tp = {0.f, 0.f, 0.f, 0.f}, p_cd = p_tp, p_ps = p_tp;
+    const float* pos_row = nullptr;
+    if constexpr (EMB) {
+        int m9 = (sv.t - 1) % 9; if (m9 < 0) m9 += 9;
+        pos_row = em.postab + (size_t)min(T + sv.t + 2, em.pos_rows - 1) * em.H;      // (the row behind the last step is never consumed: clamped)
+        p_tp = *reinterpret_cast<const f32x4*>(em.tokpos + (size_t)(m9 + 3) * em.H + c0);
+        p_cd = *reinterpret_cast<const f32x4*>(em.cond + em.H + c0);                  // cond_embed row 1 (generated tokens)
+        p_ps = *reinterpret_cast<const f32x4*>(pos_row + c0);
+    }
     if (!do_sample) {
         if (nparts > 0) {            // per-block partials of the lm_head GEMV (eos already excluded there when suppressed): reduced above
         } else {                     // batched MFMA lm_head: plain logits
@@ -193,19 +218,51 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
         float* lo = sv.logits_out + (size_t)(sv.t - sv.logits_first) * V;
         for (int i = tid; i < V; i += 256) lo[i] = logits[i];
     }
+    // every thread works the fed token out for itself (`chosen` is behind the barrier above, the rest is the state record each thread holds)
+    const int t = sv.t;
+    int tok = chosen;
+    if (sv.finished) tok = TOK_PAD;
+    const int picked = tok;
+    // teacher forcing (ma_sample_cfg.forced_tokens): the pick is reported, the given token is fed
+    // (an id outside [0, V) would index the codebook / extra-embed tables out of bounds in the next embedding: clamped here;
+    //  Engine.generate refuses such a buffer on the host side)
+    if (sv.forced && t < sv.max_new) { const long long f = sv.forced[t]; tok = (int)(f < 0 ? 0 : f >= V ? V - 1 : f); }
+    f32x4 p_row = {0.f, 0.f, 0.f, 0.f};
+    const int tk = min(max(tok, 0), V - 1);                  // (an all-NaN row leaves no argmax: the index stays inside the tables)
+    const bool special = tk < 3;                             // bos/eos/pad use extra_embeds, no Linear (shape_opt.py:240-241)
+    const float* tok_row = nullptr;
+    if constexpr (EMB) {
+        tok_row = special ? em.extra + (size_t)tk * em.H : em.table + (size_t)(tk - 3) * em.H;
+        p_row = *reinterpret_cast<const f32x4*>(tok_row + c0);
+        if (special) p_tp = *reinterpret_cast<const f32x4*>(em.tokpos + (size_t)tk * em.H + c0);      // (block-uniform)
+    }
     if (tid == 0) {
-        const int t = sv.t;
-        int tok = chosen;
-        if (sv.finished) tok = TOK_PAD;
-        if (t < sv.max_new) tokens_out[t] = tok;
-        // teacher forcing (ma_sample_cfg.forced_tokens): the pick is reported, the given token is fed
-        // (an id outside [0, V) would index the codebook / extra-embed tables out of bounds in the next embedding launch: clamped here;
-        //  Engine.generate refuses such a buffer on the host side)
-        if (sv.forced && t < sv.max_new) { const long long f = sv.forced[t]; tok = (int)(f < 0 ? 0 : f >= V ? V - 1 : f); }
+        if (t < sv.max_new) tokens_out[t] = picked;
         if (tok == TOK_EOS) st->finished = 1;
         st->cur_tok = tok;
         st->t = t + 1;
         st->pos = T + t;          // next step feeds token t at cache row cond_length + (t+1) - 1
+    }
+    if constexpr (EMB) {
+        // e = (extra[tok] | table[tok - 3]) + token_embed_positions[slot] + cond_embed[1] + embed_positions[T + t' - 1 + 2], in the
+        // order of gemv_kernel's EPI_EMBED epilogue
+        float* eo = em.e_out + (size_t)blockIdx.x * em.e_stride;
+        f32x4 e = p_row;
+        e += p_tp;
+        e += p_cd;
+        e += p_ps;
+        if (tid * 4 < em.H) *reinterpret_cast<f32x4*>(eo + c0) = e;
+        if (em.H > 1024) {                                   // wider rows: the chunks behind the first 1024 columns
+            int m9 = (t - 1) % 9; if (m9 < 0) m9 += 9;
+            const float* tp_row = em.tokpos + (size_t)(special ? tk : m9 + 3) * em.H;
+            for (int c = tid * 4 + 1024; c < em.H; c += 1024) {
+                f32x4 x = *reinterpret_cast<const f32x4*>(tok_row + c);
+                x += *reinterpret_cast<const f32x4*>(tp_row + c);
+                x += *reinterpret_cast<const f32x4*>(em.cond + em.H + c);
+                x += *reinterpret_cast<const f32x4*>(pos_row + c);
+                *reinterpret_cast<f32x4*>(eo + c) = x;
+            }
+        }
     }
 }
 

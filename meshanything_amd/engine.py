@@ -282,6 +282,13 @@ class Engine:
         self._check(self.lib.ma_engine_read_logits(self.h, row, _ptr(out), _stream_ptr()))
         return out
 
+    def embed_rows(self, row0: int, n: int, from_table: bool) -> torch.Tensor:
+        """Test aid (ma_engine_embed_rows): (n, hidden) fp32 -- rows row0 .. row0 + n - 1 of the decode step's embedding table (option
+        embed_table), or what the step's embedding launch computes for the tokens row0 + 3 .. in front of its positional adds."""
+        out = torch.empty(n, self.cfg.hidden, dtype=torch.float32, device=self.device)
+        self._check(self.lib.ma_engine_embed_rows(self.h, 0 if from_table else 1, int(row0), int(n), _ptr(out), _stream_ptr()))
+        return out
+
     def persist_trace(self, kv_len: int) -> np.ndarray:
         """(256 workgroups, n_events) 100 MHz ticks of one persistent step: start, per edge {sweep start, gather done}, end."""
         out = np.zeros(256 * (320 + 512), dtype=np.uint64)
