@@ -278,6 +278,24 @@ MA_API int  ma_op_rows_prologue(int pro, const float *x, int nparts, int B, cons
                                 const float *ln_b, float ln_eps, const float *attn_ws, int attn_heads, float *xn_out,
                                 void *xb_out, int K, void *stream);
 
+/* ---- the token pick and the coordinate argmax on the caller's data (csrc/misc.hpp).  Need no engine; errors via ma_last_error(NULL); every
+ * argument is checked before the first launch; all arrays are device memory.
+ * ma_op_pick: one decode step's pick_kernel (replaces: [3p] GenerationMixin greedy / sample with TopKLogitsWarper + TopPLogitsWarper and the
+ *   generate() bookkeeping, call site meshanything.py:143-162) for B independent rows at step t, one workgroup per row.
+ *   logits (B, V) fp32, 3 <= V <= 11264 (the sampler's LDS stage).  nparts > 0: greedy reduces the lm_head's argmax partials part_val / part_idx
+ *   (B, nparts) (eos already excluded there when suppressed) instead of sweeping the logits; nparts == 0: both may be NULL.
+ *   do_sample: top_k in [1, 64], top_p in (0, 1]; row b's draw is uniforms[b * max_new + t] (uniforms (B, max_new), needs t < max_new), or with
+ *   uniforms == NULL the hashed stream of (seed, b, t).  finished (B) int32, in and out: a finished row reports and feeds pad; feeding eos
+ *   finishes the row.  forced (B, max_new) int64 or NULL: forced[b * max_new + t], clamped to [0, V), is fed instead of the pick when t < max_new.
+ *   tokens (B, max_new) int64: tokens[b * max_new + t] = the reported token when t < max_new, nothing otherwise.  cur_tok (B) int32: the fed
+ *   token.  Synchronises `stream`.
+ * ma_op_coords_argmax: coords[i] = argmax(logits[i, :]) / nd - 0.5 (lowest index wins ties) for the nf * 9 rows of logits (nf * 9, nd), NaN
+ *   where mask[i / 9] == 0 (mask: nf bytes) (replaces: meshanything.py:69-78 + undiscretize, 214-223).  1 <= nf <= 2^24, nd >= 1. */
+MA_API int  ma_op_pick(const float *logits, int B, int V, const float *part_val, const int32_t *part_idx, int nparts, int do_sample, int top_k,
+                       float top_p, int suppress_eos, const float *uniforms, uint64_t seed, int t, int max_new, const int64_t *forced,
+                       int32_t *finished, int64_t *tokens, int32_t *cur_tok, void *stream);
+MA_API int  ma_op_coords_argmax(const float *logits, int nf, int nd, const uint8_t *mask, float *coords, void *stream);
+
 /* ---- test aid: holds `n_blocks` workgroups of `lds_bytes` of LDS each (163840 = a whole CU) on the device for `microseconds`
  * (bounded: <= 2 s) on `stream`, doing nothing; ends early once `*release` (device-visible host memory, may be NULL) is non-zero.  Lets a test take CUs away from the engine's stream and check that the fused decode
  * launches -- which need their whole grid resident -- fall back to the five-launch chain instead of failing the request.  Has no

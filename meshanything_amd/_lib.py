@@ -90,6 +90,8 @@ SIGNATURES = {
     "ma_op_gemm_dec_ln": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     "ma_op_gemm_dec_qkv": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_size_t, _P]),
     "ma_op_rows_prologue": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _I, _P, _P, _I, _P]),
+    "ma_op_pick": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _F, _I, _P, C.c_uint64, _I, _I, _P, _P, _P, _P, _P]),
+    "ma_op_coords_argmax": (_I, [_P, _I, _I, _P, _P, _P]),
     "ma_op_occupy_cus": (_I, [_I, _I, C.c_int64, _P, _P]),
     "ma_op_stream_copy": (_I, [_P, _P, C.c_size_t, _I, _P]),
     "ma_op_set_half_dtype": (_I, [_I]),

@@ -563,6 +563,53 @@ int ma_op_rows_prologue(int pro, const float* x, int nparts, int B, const float*
     });
 }
 
+// the decode step's token pick on the caller's logits: pick_kernel<false> as enqueue_pick launches it (one block per row, V floats of dynamic LDS),
+// on state records built here for step t
+int ma_op_pick(const float* logits, int B, int V, const float* part_val, const int32_t* part_idx, int nparts, int do_sample, int top_k, float top_p,
+               int suppress_eos, const float* uniforms, uint64_t seed, int t, int max_new, const int64_t* forced, int32_t* finished, int64_t* tokens,
+               int32_t* cur_tok, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!logits || !finished || !tokens || !cur_tok) throw MaError(MA_ERR_INVALID, "ma_op_pick: null pointer");
+        if (B < 1 || B > 65535 || V < 3) throw MaError(MA_ERR_INVALID, "ma_op_pick: need 1 <= B <= 65535 and V >= 3");
+        // (validate_config, engine_build.hpp: the V logits in dynamic LDS next to ~19 KB of static LDS, 64 KB per workgroup)
+        if ((size_t)V * 4 + 20 * 1024 > 64 * 1024) throw MaError(MA_ERR_INVALID, "ma_op_pick: V too large for the sampler's LDS stage (max 11264)");
+        if (nparts < 0 || nparts > V || (nparts > 0 && (!part_val || !part_idx))) throw MaError(MA_ERR_INVALID, "ma_op_pick: nparts must be in [0, V], with both partial arrays when > 0");
+        if (t < 0 || max_new < 1) throw MaError(MA_ERR_INVALID, "ma_op_pick: need t >= 0 and max_new >= 1");
+        if (do_sample && (top_k < 1 || top_k > PICK_KMAX)) throw MaError(MA_ERR_INVALID, "ma_op_pick: top_k must be in [1,64]");
+        if (do_sample && !(top_p > 0.f && top_p <= 1.f)) throw MaError(MA_ERR_INVALID, "ma_op_pick: top_p must be in (0,1]");
+        if (do_sample && uniforms && t >= max_new) throw MaError(MA_ERR_INVALID, "ma_op_pick: step t has no injected uniform (t >= max_new)");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        DecState* st = nullptr;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&st), (size_t)B * sizeof(DecState)));
+        try {
+            DecState v{};
+            v.suppress_eos = suppress_eos ? 1 : 0; v.do_sample = do_sample ? 1 : 0; v.top_k = top_k; v.top_p = top_p; v.seed = seed;
+            v.uniforms = uniforms; v.max_new = max_new; v.forced = reinterpret_cast<const long long*>(forced);
+            hipLaunchKernelGGL(init_state_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, st, v, B, V);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(pick_state_in_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, st, t, finished, B);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(pick_kernel<false>, dim3(B), dim3(256), (size_t)V * sizeof(float), s, logits, V, part_val, part_idx, nparts, nparts, st,
+                               reinterpret_cast<long long*>(tokens), max_new, 0, PickEmbed{});
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(pick_state_out_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, st, finished, cur_tok, B);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(s));
+        } catch (...) { (void)hipFree(st); throw; }
+        HIP_CHECK(hipFree(st));
+    });
+}
+
+// the detokenizer's per-coordinate argmax (detok_chunk's last launch) on the caller's logits
+int ma_op_coords_argmax(const float* logits, int nf, int nd, const uint8_t* mask, float* coords, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!logits || !mask || !coords) throw MaError(MA_ERR_INVALID, "ma_op_coords_argmax: null pointer");
+        if (nf < 1 || nf > (1 << 24) || nd < 1) throw MaError(MA_ERR_INVALID, "ma_op_coords_argmax: need 1 <= nf <= 2^24 and nd >= 1");
+        hipLaunchKernelGGL(coords_argmax_kernel, dim3(ceil_div(nf * 9, 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, nf, nd, mask, coords);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int ma_op_occupy_cus(int n_blocks, int lds_bytes, int64_t microseconds, const int32_t* release, void* stream) {
     return guarded(nullptr, [&] {
         if (n_blocks < 1 || n_blocks > 4096 || lds_bytes < 64 || lds_bytes > 160 * 1024 || microseconds < 1 || microseconds > 2000000)

@@ -138,7 +138,8 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
         for (int i = tid; i < V; i += 256) dyn[i] = (st->suppress_eos && i == TOK_EOS) ? -INFINITY : logits[i];
         if (tid == 0) { sel_prefix = 0u; sel_krem = (unsigned)k; ncand = 0; }
         __syncthreads();
-        auto key_of = [](float f) -> unsigned { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
+        // (-0 takes +0's key: "score >= the k-th largest" is a float comparison, in which the two are one value)
+        auto key_of = [](float f) -> unsigned { const unsigned u = __float_as_uint(f); return u == 0x80000000u ? u : (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
         for (int shift = 24; shift >= 0; shift -= 8) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) hist[c * 256 + tid] = 0u;
@@ -177,6 +178,31 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
             }
         }
         __syncthreads();
+        if (ncand > PICK_KMAX) {                          // (block-uniform)
+            // ties at the threshold left more candidates than slots, and the atomics above handed the slots out in arrival order.  The kept
+            // set is the PICK_KMAX best under (score descending, index ascending): the scores above the threshold (fewer than k, in any
+            // order: they are ranked below), then threshold-equal ones by ascending index (wave 0 walks the row, a ballot per 64 logits)
+            __syncthreads();                              // everyone has read ncand
+            if (tid == 0) ncand = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += 256) {
+                if (key_of(dyn[i]) > thr) { const int slot = atomicAdd(&ncand, 1); if (slot < PICK_KMAX) { cv[slot] = dyn[i]; ci[slot] = i; } }
+            }
+            __syncthreads();
+            if (w == 0) {
+                int n = ncand;                            // < k <= PICK_KMAX
+                for (int base = 0; base < V && n < PICK_KMAX; base += 64) {
+                    const int i = base + lane;
+                    const bool eq = i < V && key_of(dyn[i]) == thr;
+                    const unsigned long long m = __ballot(eq);
+                    const int slot = n + __popcll(m & ((1ull << lane) - 1ull));
+                    if (eq && slot < PICK_KMAX) { cv[slot] = dyn[i]; ci[slot] = i; }
+                    n += __popcll(m);
+                }
+                if (lane == 0) ncand = min(n, PICK_KMAX);
+            }
+            __syncthreads();
+        }
         const int nc = min(ncand, PICK_KMAX);
         // order the candidates: descending score, ties by ascending index (rank by counting, one wave)
         __shared__ float sv[PICK_KMAX]; __shared__ int si[PICK_KMAX];
@@ -275,6 +301,20 @@ __global__ void init_state_kernel(DecState* st, DecState v, int B, int V) {
     if (v.forced) v.forced += (size_t)b * v.max_new;
     if (v.logits_out) v.logits_out += (size_t)b * (v.max_new - v.logits_first) * V;
     st[b] = v;
+}
+// kernel-level entry point ma_op_pick: the step index and the caller's per-row finished flags into the records init_state_kernel wrote ...
+__global__ void pick_state_in_kernel(DecState* st, int t, const int* __restrict__ finished, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    st[b].t = t;
+    st[b].finished = finished[b] != 0;
+}
+// ... and what the pick left in them back into the caller's arrays
+__global__ void pick_state_out_kernel(const DecState* st, int* __restrict__ finished, int* __restrict__ cur_tok, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    finished[b] = st[b].finished;
+    cur_tok[b] = st[b].cur_tok;
 }
 // used by stepwise prefill / profiling: set the fields one decode step reads (all rows)
 __global__ void set_pos_kernel(DecState* st, int t, int pos, int cur_tok, int B) {

@@ -32,7 +32,7 @@ def _declared_symbols():
 
 def test_every_declared_symbol_is_exported_and_bound(lib):
     declared = _declared_symbols()
-    assert len(declared) >= 28
+    assert len(declared) >= 58
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     for name in declared:
         assert getattr(lib, name) is not None
