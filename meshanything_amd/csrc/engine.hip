@@ -17,6 +17,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/meshanything_amd.h"
@@ -668,15 +669,16 @@ int ma_profile_decode(ma_engine* e, int kv_len, int steps, ma_kernel_timing* out
         // decode_groups > 1; the per-class and eager figures are always one ungrouped chain on `s`).
         auto timed = [&](int only_cls, int* launches) -> float {
             StepTimer tm; tm.only_cls = only_cls;
+            Step step(e, s, tm, Rows{0, B});
             reset();
             if (only_cls == -2) launch_steps(e, s, B, impl, 1);                                   // warm
-            else { StepTimer w; w.only_cls = only_cls; enqueue_decode_step(e, s, -1, w, Rows{0, B}, impl); }
+            else { StepTimer w; w.only_cls = only_cls; Step warm(e, s, w, Rows{0, B}); enqueue_decode_step(warm, impl); }
             reset();
             HIP_CHECK(hipEventRecord(a, s));
             if (only_cls == -2) launch_steps(e, s, B, impl, steps);          // what generate() runs: row groups on their streams, joined on s
             else for (int i = 0; i < steps; ++i) {
-                enqueue_decode_step(e, s, -1, tm, Rows{0, B}, impl);
-                if (only_cls >= 0 && only_cls != 3) {
+                enqueue_decode_step(step, impl);
+                if (only_cls >= 0 && only_cls != CLS_PICK) {
                     // without the pick launch the state would not advance, and the fused launches tag their in-launch exchanges
                     // with the cache position: move it by hand (one tiny launch per step, charged to the class being timed)
                     hipLaunchKernelGGL(set_pos_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, e->d_st, kv_len - e->T + i + 1, kv_len + i, 5, B);
@@ -692,8 +694,8 @@ int ma_profile_decode(ma_engine* e, int kv_len, int steps, ma_kernel_timing* out
         };
         out->step_ms_eager = timed(-1, nullptr) / steps;
         if (e->cfg.use_graph) out->step_ms_graph = timed(-2, nullptr) / steps;
-        for (int cls : {0, 1, 2, 3}) {
-            if ((impl == 1) != (cls == 2)) continue;          // the persistent step is one launch of its own class
+        for (LaunchClass cls : {CLS_WEIGHTS, CLS_ATTN, CLS_PERSIST, CLS_PICK}) {
+            if ((impl == 1) != (cls == CLS_PERSIST)) continue;          // the persistent step is one launch of its own class
             int n = 0;
             out->ms[cls] = timed(cls, &n);
             out->launches[cls] = n;
@@ -720,10 +722,12 @@ int ma_trace_decode(ma_engine* e, int kv_len, uint64_t* host_out, int max_launch
         try {
             HIP_CHECK(hipMemsetAsync(d_tr, 0, n64 * sizeof(unsigned long long), s));
             StepTimer none;
-            for (int i = 0; i < 3; ++i) enqueue_decode_step(e, s, -1, none, Rows{0, TB});            // warm: clocks, caches
-            std::vector<int> k, b;
+            Step warm(e, s, none, Rows{0, TB});
+            for (int i = 0; i < 3; ++i) enqueue_decode_step(warm);            // warm: clocks, caches
+            std::vector<int> k, b;                                            // TraceKind per traced launch, its blocks
             StepTimer tm; tm.tr = d_tr; tm.tr_max_launches = max_launches; tm.tr_max_blocks = max_blocks; tm.tr_kind = &k; tm.tr_blocks = &b;
-            enqueue_decode_step(e, s, -1, tm, Rows{0, TB});
+            Step traced(e, s, tm, Rows{0, TB});
+            enqueue_decode_step(traced);
             HIP_CHECK(hipMemcpyAsync(host_out, d_tr, n64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
             *n_launches = (int)k.size();
@@ -774,12 +778,14 @@ int ma_engine_embed_rows(ma_engine* e, int what, int row0, int n, float* out, vo
         HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&z), zrows * H * sizeof(float)));
         try {
             HIP_CHECK(hipMemsetAsync(z, 0, zrows * H * sizeof(float), s));
+            StepTimer none;
+            const Step row0_step(e, s, none, Rows{0, 1});
             for (int i = 0; i < n; ++i) {
                 hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(64), 0, s, e->d_st, 0, e->T - 1, row0 + i + 3, 1);
                 HIP_CHECK(hipGetLastError());
-                GemvArgs a = make_embed_args(e, Rows{0, 1});
+                GemvArgs a = make_embed_args(row0_step);
                 a.tokpos = z; a.cond = z; a.postab = z; a.y = out + (size_t)i * H;
-                gemv(e, a, s, 1);
+                gemv_launch(e, a, s, 1);
             }
             HIP_CHECK(hipStreamSynchronize(s));
         } catch (...) { (void)hipFree(z); throw; }

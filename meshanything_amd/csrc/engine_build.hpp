@@ -1,4 +1,4 @@
-// Engine construction and destruction: configuration checks, device buffers, residency gates of the fused launches. (No includes of its own: compiled only inside engine.hip, in its include order.)
+// Engine construction and destruction: configuration checks, the weight records of the dense phases and of the decode step (a missing name fails here), device buffers (the in-launch exchanges through xalloc), residency gates of the fused launches. (No includes of its own: compiled only inside engine.hip, in its include order.)
 #pragma once
 
 namespace {
@@ -20,8 +20,8 @@ void validate_config(const ma_config& c) {
     if ((size_t)(c.codebook_size + 3) * 4 + 20 * 1024 > 64 * 1024) bad("codebook_size too large for the sampler's LDS stage (max 11261)");
 }
 
-// every matrix / bias / LayerNorm pair of the dense phases, by its arena name, into e->dw (engine_state.hpp)
-void resolve_dense_weights(ma_engine* e) {
+// every matrix / bias / LayerNorm pair of the dense phases, by its arena name, into e->dw, and the decode step's tables into e->decw (engine_state.hpp)
+void resolve_weights(ma_engine* e) {
     const ma_config& c = e->cfg;
     auto lin = [&](const std::string& p, bool bias = true) {
         const Entry& en = e->entry(p + ".weight");
@@ -49,6 +49,8 @@ void resolve_dense_weights(ma_engine* e) {
         const std::string p = TOK + "decoder.layer." + std::to_string(n) + ".";
         w.bert.push_back(PostLnLayerW{lin(p + "qkv"), lin(p + "attention.output.dense"), lin(p + "intermediate.dense"), lin(p + "output.dense"), ln(p + "attention.output.LayerNorm", 1e-12f), ln(p + "output.LayerNorm", 1e-12f)});
     }
+    e->decw = DecW{e->P("transformer.lm_head.weight"), e->P(DEC + "input_layer.weight"), e->PF(DEC + "input_layer.bias"), w.codebooks, e->PF(DEC + "extra_embeds.weight"),
+                   e->PF(DEC + "token_embed_positions.weight"), w.cond_embed, w.embed_pos, e->entry(DEC + "embed_positions.weight").rows};
 }
 
 void build_engine(ma_engine* e) {
@@ -75,24 +77,17 @@ void build_engine(ma_engine* e) {
     e->d_pval = e->dmalloc<float>(MB * e->V); e->d_pidx = e->dmalloc<int>(MB * e->V);        // row stride V >= blocks for any rows-per-block
     e->d_st = e->dmalloc<DecState>(MB);
     e->d_embtab = e->dmalloc<float>((size_t)c.codebook_size * H);      // (ensure_embtab fills it)
-    e->d_qkv_gran = e->dmalloc<u64>(MB * 3 * H); e->d_chain_err = e->dmalloc<unsigned>(12);      // [0] error bits (cleared when read), [1] expiries ever, [2] longest slow block (ticks), [3] slow blocks ever, [4] scalar sweeps rescued by a vector look (rows_attn.hpp)
-    e->d_y1_gran = e->dmalloc<u64>(MB * H);
-    HIP_CHECK(hipMemset(e->d_y1_gran, 0, MB * H * sizeof(u64)));
-    e->d_attn_pair_gran = e->dmalloc<unsigned long long>(MB * c.heads * ATTN_PAIR_GRANULES);
-    HIP_CHECK(hipMemset(e->d_attn_pair_gran, 0, MB * c.heads * ATTN_PAIR_GRANULES * sizeof(unsigned long long)));
-    e->d_y2_gran = e->dmalloc<u64>(MB * H);
-    HIP_CHECK(hipMemset(e->d_y2_gran, 0, MB * H * sizeof(u64)));
-    e->d_ra_qkv_gran = e->dmalloc<u64>(MB * RA_QKV_GRANULES); e->d_ra_out_gran = e->dmalloc<u64>(MB * RA_OUT_GRANULES);
-    HIP_CHECK(hipMemset(e->d_ra_qkv_gran, 0, MB * RA_QKV_GRANULES * sizeof(u64)));
-    HIP_CHECK(hipMemset(e->d_ra_out_gran, 0, MB * RA_OUT_GRANULES * sizeof(u64)));
+    // the in-launch exchanges (xalloc: zeroed here and again for every generation, because their epochs are tagged with the cache position, which restarts)
+    e->d_qkv_gran = e->xalloc<u64>(MB * 3 * H);
+    e->d_chain_err = e->xalloc<unsigned>(12, 1);      // [0] error bits (cleared when read, and per generation), [1] expiries ever, [2] longest slow block (ticks), [3] slow blocks ever, [4] scalar sweeps rescued by a vector look (rows_attn.hpp)
+    e->d_y1_gran = e->xalloc<u64>(MB * H);
+    e->d_attn_pair_gran = e->xalloc<unsigned long long>(MB * c.heads * ATTN_PAIR_GRANULES);
+    e->d_y2_gran = e->xalloc<u64>(MB * H);
+    e->d_ra_qkv_gran = e->xalloc<u64>(MB * RA_QKV_GRANULES); e->d_ra_out_gran = e->xalloc<u64>(MB * RA_OUT_GRANULES);
     e->d_pf_sink = e->dmalloc<unsigned>(4);
-    e->d_rm_y2_gran = e->dmalloc<u64>(MB * RM_Y2_GRANULES);
-    HIP_CHECK(hipMemset(e->d_rm_y2_gran, 0, MB * RM_Y2_GRANULES * sizeof(u64)));
-    e->d_ffn_gran = e->dmalloc<u64>(MB * (size_t)c.ffn);
-    HIP_CHECK(hipMemset(e->d_ffn_gran, 0, MB * (size_t)c.ffn * sizeof(u64)));
+    e->d_rm_y2_gran = e->xalloc<u64>(MB * RM_Y2_GRANULES);
+    e->d_ffn_gran = e->xalloc<u64>(MB * (size_t)c.ffn);
     exp_alloc_exchanges(e);
-    HIP_CHECK(hipMemset(e->d_qkv_gran, 0, MB * 3 * H * sizeof(u64)));
-    HIP_CHECK(hipMemset(e->d_chain_err, 0, 12 * sizeof(unsigned)));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_chain_err), sizeof(unsigned)));
     e->d_xb = e->dmalloc<bf16_t>(MB * H); e->d_ffb = e->dmalloc<bf16_t>(MB * c.ffn);
     e->d_ks_o = e->dmalloc<float>(4 * MB * H); e->d_ks_f = e->dmalloc<float>(4 * MB * H);
@@ -159,8 +154,7 @@ void build_engine(ma_engine* e) {
         e->p_y_part_stride = (long)(PS * H);
         e->p_h = e->dmalloc<float>(PR * H); e->p_y = e->dmalloc<float>(std::max(PR, 4 * PS) * H);
         e->ln_gran_tiles = (PR / 256 + 1) * (size_t)((H + 255) / 256);
-        e->d_ln_gran = e->dmalloc<u64>(2 * e->ln_gran_tiles * 256);
-        HIP_CHECK(hipMemset(e->d_ln_gran, 0, 2 * e->ln_gran_tiles * 256 * sizeof(u64)));
+        e->d_ln_gran = e->xalloc<u64>(2 * e->ln_gran_tiles * 256, 0);      // (its epoch counter, ln_epoch, runs on across generations)
         e->a_ph = amalloc(PR * H); e->a_pqkv = amalloc(PR * 3 * H); e->a_patt = amalloc(PR * H); e->a_pffn = amalloc(PR * c.ffn);
         if (e->bf16) {
             e->a_patt_tail = amalloc((size_t)64 * H);
@@ -170,7 +164,7 @@ void build_engine(ma_engine* e) {
     const size_t B = c.max_batch;
     e->w_latents = e->dmalloc<float>(B * T * W); e->w_prefix = e->dmalloc<float>(B * T * H);
     e->w_tokens = e->dmalloc<long long>(B * e->maxnew); e->w_ids = e->dmalloc<long long>(B * (size_t)e->nf * 9);
-    resolve_dense_weights(e);
+    resolve_weights(e);
     // per-layer decode pointers: the matrices the prefill runs, as the decode kernels take them
     e->dl.resize(c.layers);
     for (int l = 0; l < c.layers; ++l) {

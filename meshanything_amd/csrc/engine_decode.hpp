@@ -1,19 +1,25 @@
 // One decode step as a chain of launches (GEMV chain: batch 1 and small batches; matrix-core chain: 4 .. 64 rows under a 16-bit policy),
-// its capture into one hipGraph per row range, and row groups. (No includes of its own: compiled only inside engine.hip, in its include order.)
+// its capture into one hipGraph per row range, and row groups.  Everything that enqueues takes a `Step`: engine, stream, timer and the row
+// range's view of every per-row buffer, sliced in ONE place (its constructor); the weights come resolved (e->dl, e->dw.opt[l].ln1 / ln2,
+// e->decw), so a step builds no names and looks nothing up.  (No includes of its own: compiled only inside engine.hip, in its include order.)
 #pragma once
 
 namespace {
 
 int gemv_blocks(ma_engine* e, int N, int K) { return e->bf16 ? gemv_num_blocks<bf16_t>(N, K) : gemv_num_blocks<float>(N, K); }     // (the two 16-bit formats share their shapes)
 
+// The values are part of the ABI: launch classes index ma_kernel_timing, trace kinds fill the `kinds` array of ma_trace_decode.
+enum LaunchClass { CLS_WEIGHTS = 0, CLS_ATTN = 1, CLS_PERSIST = 2, CLS_PICK = 3 };      // weight-streaming launches | attention, and launches that contain one | the persistent step | the pick
+enum TraceKind { TK_EMBED = 0, TK_QKV = 1, TK_ATTN = 2, TK_OPROJ = 3, TK_FC1 = 4, TK_FC2 = 5, TK_LMHEAD = 6 };
+
 struct StepTimer {                    // launch filter (ma_profile_decode) / in-kernel timestamps (ma_trace_decode)
-    int only_cls = -1;                // >= 0: enqueue only the launches of this class (0 gemv, 1 attention, 3 pick)
+    int only_cls = -1;                // >= 0: enqueue only the launches of this LaunchClass
     int launched[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool on(int c) { if (only_cls >= 0 && c != only_cls) return false; launched[c]++; return true; }
+    bool on(LaunchClass c) { if (only_cls >= 0 && c != only_cls) return false; launched[c]++; return true; }
     unsigned long long* tr = nullptr; int tr_max_launches = 0, tr_max_blocks = 0;
     std::vector<int>* tr_kind = nullptr; std::vector<int>* tr_blocks = nullptr;
-    // slot for the next launch's timestamps (kind: 0 embed, 1 qkv, 2 attention, 3 out_proj, 4 fc1, 5 fc2, 6 lm_head)
-    unsigned long long* trace_slot(int kind, int blocks) {
+    // slot for the next launch's timestamps
+    unsigned long long* trace_slot(TraceKind kind, int blocks) {
         if (!tr || (int)tr_kind->size() >= tr_max_launches || blocks > tr_max_blocks) return nullptr;
         unsigned long long* p = tr + (size_t)tr_kind->size() * tr_max_blocks * 4;
         tr_kind->push_back(kind); tr_blocks->push_back(blocks);
@@ -25,15 +31,7 @@ struct StepTimer {                    // launch filter (ma_profile_decode) / in-
 // buffer, its own KV planes, its own DecState record and its own output token row; the weights are shared.
 struct Rows { int r0 = 0, B = 1; };
 
-GemvArgs gemv_base(ma_engine* e, Rows rw) {
-    GemvArgs a{};
-    a.round_x = e->bf16 ? 1 : 0;
-    a.st = e->d_st + rw.r0;
-    a.act = ACT_NONE;
-    a.epi = EPI_PLAIN;
-    return a;
-}
-void gemv(ma_engine* e, const GemvArgs& a, hipStream_t s, int B) {
+void gemv_launch(ma_engine* e, const GemvArgs& a, hipStream_t s, int B) {
     launched(PREC_CALL(e->bf16, e->hdt, T, launch_gemv<T>(a, s, B)), "gemv");
 }
 
@@ -42,27 +40,7 @@ bool use_mfma_decode(ma_engine* e, int B) { return e->bf16 && B >= e->opt.mfma_m
 // input of a batched prologue: either a plain fp32 buffer, or the raw partials of a split-K GEMM plus its deferred epilogue
 struct ProIn { const float* x = nullptr; int nparts = 1; const float* bias = nullptr; const float* res = nullptr; };
 
-void rows_prologue(ma_engine* e, hipStream_t s, int pro, Rows rw, ProIn in, const float* g, const float* b, float* xn_out, StepTimer& tm) {
-    if (!tm.on(0)) return;
-    const ma_config& c = e->cfg;
-    RowsProArgs a{};
-    a.x = in.x; a.x_stride = c.hidden; a.nparts = in.nparts; a.B = rw.B; a.bias = in.bias; a.res = in.res; a.res_stride = c.hidden;
-    a.ln_g = g; a.ln_b = b; a.ln_eps = 1e-5f;
-    a.attn_ws = e->d_part + (size_t)rw.r0 * attn_workspace_floats(c.heads); a.attn_ws_stride = attn_workspace_floats(c.heads); a.attn_heads = c.heads;
-    a.xn_out = xn_out; a.xn_stride = c.hidden; a.xb = e->d_xb + (size_t)rw.r0 * c.hidden; a.xb_stride = c.hidden; a.K = c.hidden;
-    launched(H16_CALL(e->hdt, HT, launch_rows_prologue<HT>(a, pro, rw.B, s)), "rows_prologue");
-}
-// kind: the timeline's launch kind (StepTimer::trace_slot)
-void gemm_dec_ln(ma_engine* e, hipStream_t s, GemmDecArgs a, StepTimer& tm, int kind) {
-    if (!tm.on(0)) return;
-    a.trace = tm.trace_slot(kind, (a.N + 15) / 16);
-    launched(H16_CALL(e->hdt, HT, launch_gemm_dec_ln<HT>(a, s, e->opt.mfma_ln_waves)), "gemm_dec_ln");
-}
-void gemm_dec(ma_engine* e, hipStream_t s, GemmDecArgs a, StepTimer& tm, int kind) {
-    if (!tm.on(0)) return;
-    a.trace = tm.trace_slot(kind, (a.N + 15) / 16 * std::max(1, a.ksplit));
-    launched(H16_CALL(e->hdt, HT, launch_gemm_dec<HT>(a, s)), "gemm_dec");
-}
+const LnW NO_LN{nullptr, nullptr, 1e-5f};      // a prologue without LayerNorm (the launch still carries the eps)
 
 // The gates of the two 8-row launches (rows_attn.hpp, rows_mlp.hpp) that do not depend on the layer -- ONE definition for the step builder
 // below and for ma_engine_get_option("fuse_rows_attn" / "fuse_rows_mlp"), which bench.py uses to label the roofline kernel.
@@ -89,33 +67,107 @@ RowsGates rows_gates(ma_engine* e, int B, int len_override) {
     return g;
 }
 
-// the pointer set of one step of a row range: row b owns the b-th slice of every buffer
-struct MfmaStep {
+// One step of one row range: who enqueues (engine, stream, timer), for which rows, and those rows' slice of every per-row buffer -- row b of the
+// range owns the b-th slice of each.  The constructor is the only place that slices.
+// The launch helpers share one order: the class filter first, then the trace slot.  (A launch that is filtered out takes no slot; a trace never
+// runs with a filter, so the recorded sequence does not depend on the order.)
+struct Step {
     ma_engine* e; hipStream_t s; StepTimer& tm; Rows rw; int len_override;
-    RowsGates rg;
-    int ks_o;                          // split of out_proj along K: 1 when LayerNorm 1 runs inside fc1 (its epilogue then finishes y1)
-    float *h0, *q, *h1, *y1, *y2, *part;
+    float *de, *h0, *q, *h1, *y1, *y2, *ffn, *part;      // embedding | LayerNorm 2 output | q | LayerNorm 1 output | out_proj sum | fc2 sum | relu(fc1) | split-KV attention partials
+    bf16_t *xb, *ffb;                                    // 16-bit operands of the matrix-core chain
     // split-K partial buffers [ks][B][H] of THIS row range: the ranges of concurrently stepping row groups do not overlap
     // (4 r0 H floats in front of it belong to the rows before r0, whatever their grouping)
     float *partO, *partF;
-    bf16_t *xb, *ffb;
+    float *logits, *pval; int* pidx; DecState* st; long long* w_tokens;
     size_t kv_row_elems;
+    u64 *qkv_gran, *y1_gran, *y2_gran, *ffn_gran, *ra_qkv_gran, *ra_out_gran, *rm_y2_gran, *part_gran = nullptr; unsigned long long* pair_gran;      // in-launch exchanges
+    // the matrix-core chain's (set by mfma_chain)
+    RowsGates rg{};
+    int ks_o = 1;                      // split of out_proj along K: 1 when LayerNorm 1 runs inside fc1 (its epilogue then finishes y1)
     bool ln2_prev = false;             // the previous layer's MLP launch finished its LayerNorm 2 (rows_mlp.hpp step E): xb and h0 are ready
+
+    Step(ma_engine* e_, hipStream_t s_, StepTimer& tm_, Rows rw_, int len_override_ = -1) : e(e_), s(s_), tm(tm_), rw(rw_), len_override(len_override_) {
+        const ma_config& c = e->cfg;
+        const size_t r0 = rw.r0, H = c.hidden, V = e->V;
+        de = e->d_e + r0 * H; h0 = e->d_h0 + r0 * H; q = e->d_q + r0 * H; h1 = e->d_h1 + r0 * H; y1 = e->d_ypre1 + r0 * H; y2 = e->d_ypre2 + r0 * H;
+        ffn = e->d_ffn + r0 * c.ffn; part = e->d_part + r0 * attn_workspace_floats(c.heads);
+        xb = e->d_xb + r0 * H; ffb = e->d_ffb + r0 * c.ffn; partO = e->d_ks_o + 4 * r0 * H; partF = e->d_ks_f + 4 * r0 * H;
+        logits = e->d_logits + r0 * V; pval = e->d_pval + r0 * V; pidx = e->d_pidx + r0 * V; st = e->d_st + r0; w_tokens = e->w_tokens + r0 * e->maxnew;
+        kv_row_elems = e->kv_row_bytes / e->kv_elem;
+        qkv_gran = e->d_qkv_gran + r0 * 3 * H; y1_gran = e->d_y1_gran + r0 * H; y2_gran = e->d_y2_gran + r0 * H; ffn_gran = e->d_ffn_gran + r0 * c.ffn;
+        pair_gran = e->d_attn_pair_gran + r0 * c.heads * ATTN_PAIR_GRANULES;
+        ra_qkv_gran = e->d_ra_qkv_gran + r0 * RA_QKV_GRANULES; ra_out_gran = e->d_ra_out_gran + r0 * RA_OUT_GRANULES; rm_y2_gran = e->d_rm_y2_gran + r0 * RM_Y2_GRANULES;
+#ifdef MA_EXPERIMENTAL
+        part_gran = e->d_part_gran + r0 * c.heads * ATTN_NCHUNK * RF_PART;
+#endif
+    }
+    char* kplane(int l) const { return e->kplane(rw.r0, l); }
+    char* vplane(int l) const { return e->vplane(rw.r0, l); }
+    int H() const { return e->cfg.hidden; }
+    const DecLayerPtrs& w(int l) const { return e->dl[l]; }
+    const LnW& ln1(int l) const { return e->dw.opt[l].ln1; }
+    const LnW& ln2(int l) const { return e->dw.opt[l].ln2; }
+
+    // ---- GEMV chain
+    GemvArgs gemv_args() const {
+        GemvArgs a{};
+        a.round_x = e->bf16 ? 1 : 0; a.st = st; a.act = ACT_NONE; a.epi = EPI_PLAIN;
+        return a;
+    }
+    void gemv(GemvArgs a, TraceKind kind) {
+        if (!tm.on(CLS_WEIGHTS)) return;
+        a.trace = tm.trace_slot(kind, gemv_blocks(e, a.N, a.K));
+        gemv_launch(e, a, s, rw.B);
+    }
+    void lm_head(const float* x, int x_stride, const LnW& ln) {
+        GemvArgs a = gemv_args();
+        a.W = e->decw.lm_head; a.x = x; a.x_stride = x_stride; a.ln_g = ln.g; a.ln_b = ln.b; a.ln_eps = ln.eps;
+        a.y = logits; a.y_stride = e->V; a.N = e->V; a.K = H(); a.epi = EPI_LMHEAD;
+        a.part_val = pval; a.part_idx = pidx; a.part_stride = e->V;
+        gemv(a, TK_LMHEAD);
+    }
+
+    // ---- matrix-core chain
+    // the LayerNorm that a launch runs in front of its GEMM: `in` normalised with `ln`, the fp32 result kept in xn_out
+    template <typename A>
+    void fold_ln(A& a, const ProIn& in, const LnW& ln, float* xn_out) const {
+        a.pin = in.x; a.pin_stride = H(); a.pin_parts = in.nparts; a.pbias = in.bias; a.pres = in.res; a.pres_stride = H();
+        a.ln_g = ln.g; a.ln_b = ln.b; a.ln_eps = ln.eps; a.xn_out = xn_out; a.xn_stride = H();
+    }
+    void rows_prologue(int pro, const ProIn& in, const LnW& ln, float* xn_out) {
+        if (!tm.on(CLS_WEIGHTS)) return;
+        const ma_config& c = e->cfg;
+        RowsProArgs a{};
+        a.x = in.x; a.x_stride = c.hidden; a.nparts = in.nparts; a.B = rw.B; a.bias = in.bias; a.res = in.res; a.res_stride = c.hidden;
+        a.ln_g = ln.g; a.ln_b = ln.b; a.ln_eps = ln.eps;
+        a.attn_ws = part; a.attn_ws_stride = attn_workspace_floats(c.heads); a.attn_heads = c.heads;
+        a.xn_out = xn_out; a.xn_stride = c.hidden; a.xb = xb; a.xb_stride = c.hidden; a.K = c.hidden;
+        launched(H16_CALL(e->hdt, HT, launch_rows_prologue<HT>(a, pro, rw.B, s)), "rows_prologue");
+    }
+    void gemm_dec_ln(GemmDecArgs a, TraceKind kind) {
+        if (!tm.on(CLS_WEIGHTS)) return;
+        a.trace = tm.trace_slot(kind, (a.N + 15) / 16);
+        launched(H16_CALL(e->hdt, HT, launch_gemm_dec_ln<HT>(a, s, e->opt.mfma_ln_waves)), "gemm_dec_ln");
+    }
+    void gemm_dec(GemmDecArgs a, TraceKind kind) {
+        if (!tm.on(CLS_WEIGHTS)) return;
+        a.trace = tm.trace_slot(kind, (a.N + 15) / 16 * std::max(1, a.ksplit));
+        launched(H16_CALL(e->hdt, HT, launch_gemm_dec<HT>(a, s)), "gemm_dec");
+    }
     // y2 of a layer as the LayerNorm 2 that follows reads it: fc2's partials + deferred epilogue, or one buffer
     ProIn y2_of(int l) const {
         ProIn in;
-        if (rg.ks_f > 1) { in.x = partF; in.nparts = rg.ks_f; in.bias = e->dl[l].fc2_b; in.res = h1; } else in.x = y2;
+        if (rg.ks_f > 1) { in.x = partF; in.nparts = rg.ks_f; in.bias = w(l).fc2_b; in.res = h1; } else in.x = y2;
         return in;
     }
 };
 
 // First half of layer l: [LayerNorm 2 of layer l - 1 +] q/k/v + attention + out_proj.  Returns y1 as the second half reads it.
-ProIn mfma_attn_half(MfmaStep& p, int l, const float* x_embed) {
-    ma_engine* e = p.e; hipStream_t s = p.s; StepTimer& tm = p.tm; const Rows rw = p.rw;
+ProIn mfma_attn_half(Step& p, int l, const float* x_embed) {
+    ma_engine* e = p.e;
     const ma_config& c = e->cfg;
-    const int H = c.hidden, B = rw.B;
-    const size_t r0 = rw.r0;
-    const DecLayerPtrs& w = e->dl[l];
+    const int H = c.hidden, B = p.rw.B;
+    const DecLayerPtrs& w = p.w(l);
     const float* resid;
     ProIn qin;                                              // input of this layer's q/k/v GEMM when its LayerNorm is folded
     if (l == 0) {
@@ -124,26 +176,23 @@ ProIn mfma_attn_half(MfmaStep& p, int l, const float* x_embed) {
         resid = p.h0;
     } else {
         if (p.rg.fold) qin = p.y2_of(l - 1);
-        else rows_prologue(e, s, PRO_LN, rw, p.y2_of(l - 1), e->dl[l - 1].ln2_g, e->dl[l - 1].ln2_b, p.h0, tm);
+        else p.rows_prologue(PRO_LN, p.y2_of(l - 1), p.ln2(l - 1), p.h0);
         resid = p.h0;
     }
     const bool ln_here = p.rg.fold && l > 0 && !p.ln2_prev;     // this layer's first GEMM normalises its own input
     // 8 rows: LayerNorm 2 + q/k/v + attention + out_proj in ONE launch (rows_attn.hpp) -- three launches per layer instead of five (gates: rows_gates)
     if (p.rg.attn && (p.rg.fold || p.ln2_prev)) {
-        if (tm.on(1)) {
+        if (p.tm.on(CLS_ATTN)) {
             RowsAttnArgs a{};
             a.Wqkv = reinterpret_cast<const bf16_t*>(w.qkv_w); a.bqkv = w.qkv_b;
             if (!ln_here) { a.xb = p.xb; a.xb_stride = H; a.res = resid; a.res_stride = H; }
-            else {
-                a.pin = qin.x; a.pin_stride = H; a.pin_parts = qin.nparts; a.pbias = qin.bias; a.pres = qin.res; a.pres_stride = H;
-                a.ln_g = e->dl[l - 1].ln2_g; a.ln_b = e->dl[l - 1].ln2_b; a.ln_eps = 1e-5f; a.xn_out = p.h0; a.xn_stride = H;
-            }
-            a.kcache = reinterpret_cast<bf16_t*>(e->kplane(rw.r0, l)); a.vcache = reinterpret_cast<bf16_t*>(e->vplane(rw.r0, l)); a.kv_row_stride = p.kv_row_elems; a.max_seq = e->maxseq;
-            a.st = e->d_st + r0; a.len_override = p.len_override; a.layer = l;
-            a.qkv_gran = e->d_ra_qkv_gran + r0 * RA_QKV_GRANULES; a.pair_gran = e->d_attn_pair_gran + r0 * c.heads * ATTN_PAIR_GRANULES; a.out_gran = e->d_ra_out_gran + r0 * RA_OUT_GRANULES;
+            else p.fold_ln(a, qin, p.ln2(l - 1), p.h0);
+            a.kcache = reinterpret_cast<bf16_t*>(p.kplane(l)); a.vcache = reinterpret_cast<bf16_t*>(p.vplane(l)); a.kv_row_stride = p.kv_row_elems; a.max_seq = e->maxseq;
+            a.st = p.st; a.len_override = p.len_override; a.layer = l;
+            a.qkv_gran = p.ra_qkv_gran; a.pair_gran = p.pair_gran; a.out_gran = p.ra_out_gran;
             a.err = e->d_chain_err; a.Wo = reinterpret_cast<const bf16_t*>(w.o_w); a.bo = w.o_b; a.y1 = p.y1; a.y1_stride = H;
-            a.trace = tm.trace_slot(2, 256);
-            launched(H16_CALL(e->hdt, HT, launch_rows_attn<HT>(a, c.heads, B, s, e->opt.rows_attn_early, l == 0 ? 4 : 8)), "rows_attn");
+            a.trace = p.tm.trace_slot(TK_ATTN, 256);
+            launched(H16_CALL(e->hdt, HT, launch_rows_attn<HT>(a, c.heads, B, p.s, e->opt.rows_attn_early, l == 0 ? 4 : 8)), "rows_attn");
         }
         ProIn in1; in1.x = p.y1;
         return in1;
@@ -151,28 +200,27 @@ ProIn mfma_attn_half(MfmaStep& p, int l, const float* x_embed) {
     {
         GemmDecArgs a{};
         a.W = reinterpret_cast<const bf16_t*>(w.qkv_w); a.bias = w.qkv_b; a.xb = p.xb; a.xb_stride = H; a.y = p.q; a.y_stride = H; a.N = 3 * H; a.K = H; a.B = B; a.ksplit = 1;
-        a.epi = EPI_QKV; a.kcache = e->kplane(rw.r0, l); a.vcache = e->vplane(rw.r0, l); a.kv_row_stride = p.kv_row_elems; a.H = H; a.max_seq = e->maxseq; a.st = e->d_st + r0;
+        a.epi = EPI_QKV; a.kcache = p.kplane(l); a.vcache = p.vplane(l); a.kv_row_stride = p.kv_row_elems; a.H = H; a.max_seq = e->maxseq; a.st = p.st;
         if (ln_here) {
-            a.pin = qin.x; a.pin_stride = H; a.pin_parts = qin.nparts; a.pbias = qin.bias; a.pres = qin.res; a.pres_stride = H;
-            a.ln_g = e->dl[l - 1].ln2_g; a.ln_b = e->dl[l - 1].ln2_b; a.ln_eps = 1e-5f; a.xn_out = p.h0; a.xn_stride = H;
-            gemm_dec_ln(e, s, a, tm, 1);
-        } else gemm_dec(e, s, a, tm, 1);
+            p.fold_ln(a, qin, p.ln2(l - 1), p.h0);
+            p.gemm_dec_ln(a, TK_QKV);
+        } else p.gemm_dec(a, TK_QKV);
     }
     // 8..11 rows give only 128-176 (row, head) blocks: enough up to ~8 K cached positions, beyond that (1600-face configuration) the
     // split form streams better (profiles/r02_ab_batched_attention_forms.txt, r02_bench_config5_*).  The two-block final form needs both
     // blocks of every (row, head) resident together: 2 B heads <= CUs (8 rows on an MI355X; rows_gates pair_ok)
     if (B >= e->opt.attn_final_min_batch && (B >= 12 || p.rg.pair_ok || e->maxseq <= 8192)) {
         // enough (row, head) pairs to fill the chip: the attention launch finishes the softmax itself and writes xb
-        if (tm.on(1)) {
+        if (p.tm.on(CLS_ATTN)) {
             // 8..11 rows: two blocks per (row, head) with an in-launch hand-over, so that every CU streams (attn_decode.hpp)
             const bool pair = p.rg.pair_ok && B < 12;
-            launched(H16_CALL(e->hdt, HT, launch_attn_decode_final<HT>(p.q, e->kplane(rw.r0, l), e->vplane(rw.r0, l), c.heads, e->maxseq, e->d_st + r0, p.len_override, 1, p.xb, H, s, B, H, p.kv_row_elems,
-                                                              pair ? 8 : e->opt.attn_final_waves, pair ? e->d_attn_pair_gran + r0 * c.heads * ATTN_PAIR_GRANULES : nullptr, e->d_chain_err, l)), "attn_decode_final");
+            launched(H16_CALL(e->hdt, HT, launch_attn_decode_final<HT>(p.q, p.kplane(l), p.vplane(l), c.heads, e->maxseq, p.st, p.len_override, 1, p.xb, H, p.s, B, H, p.kv_row_elems,
+                                                              pair ? 8 : e->opt.attn_final_waves, pair ? p.pair_gran : nullptr, e->d_chain_err, l)), "attn_decode_final");
         }
     } else {
-        if (tm.on(1))
-            launched(H16_CALL(e->hdt, HT, launch_attn_decode<HT>(p.q, e->kplane(rw.r0, l), e->vplane(rw.r0, l), c.heads, e->maxseq, e->d_st + r0, p.len_override, 1, p.part, s, nullptr, B, H, p.kv_row_elems, e->opt.attn_rowwave != 0)), "attn_decode");
-        rows_prologue(e, s, PRO_ATTN, rw, ProIn{}, nullptr, nullptr, nullptr, tm);
+        if (p.tm.on(CLS_ATTN))
+            launched(H16_CALL(e->hdt, HT, launch_attn_decode<HT>(p.q, p.kplane(l), p.vplane(l), c.heads, e->maxseq, p.st, p.len_override, 1, p.part, p.s, nullptr, B, H, p.kv_row_elems, e->opt.attn_rowwave != 0)), "attn_decode");
+        p.rows_prologue(PRO_ATTN, ProIn{}, NO_LN, nullptr);
     }
     // y1 = resid + Wo a + bo
     GemmDecArgs a{};
@@ -180,57 +228,56 @@ ProIn mfma_attn_half(MfmaStep& p, int l, const float* x_embed) {
     ProIn in1;
     if (p.ks_o > 1) { a.y = p.partO; in1.x = p.partO; in1.nparts = p.ks_o; in1.bias = w.o_b; in1.res = resid; }
     else { a.y = p.y1; a.bias = w.o_b; a.res = resid; a.res_stride = H; in1.x = p.y1; }
-    gemm_dec(e, s, a, tm, 3);
+    p.gemm_dec(a, TK_OPROJ);
     return in1;
 }
 
 // Second half of layer l: LayerNorm 1 + fc1 + fc2 [+ LayerNorm 2], from y1 = in1
-void mfma_mlp_half(MfmaStep& p, int l, ProIn in1) {
-    ma_engine* e = p.e; hipStream_t s = p.s; StepTimer& tm = p.tm; const Rows rw = p.rw;
+void mfma_mlp_half(Step& p, int l, ProIn in1) {
+    ma_engine* e = p.e;
     const ma_config& c = e->cfg;
-    const int H = c.hidden, B = rw.B, L = c.layers;
-    const size_t r0 = rw.r0;
-    const DecLayerPtrs& w = e->dl[l];
+    const int H = c.hidden, B = p.rw.B, L = c.layers;
+    const DecLayerPtrs& w = p.w(l);
+    const LnW& ln1 = p.ln1(l);
     // 8 rows: LayerNorm 1 + fc1 + fc2 in ONE launch (rows_mlp.hpp): the same gates as the fused first half, and y1 complete in one buffer
     if (p.rg.mlp && in1.nparts == 1) {
         p.ln2_prev = e->opt.rows_mlp_ln2 != 0 && l + 1 < L;
-        if (!tm.on(0)) return;
+        if (!p.tm.on(CLS_WEIGHTS)) return;
         RowsMlpArgs a{};
-        a.y1 = in1.x; a.y1_stride = H; a.ln_g = w.ln1_g; a.ln_b = w.ln1_b; a.ln_eps = 1e-5f; a.h1_out = p.h1; a.h1_stride = H;
+        a.y1 = in1.x; a.y1_stride = H; a.ln_g = ln1.g; a.ln_b = ln1.b; a.ln_eps = ln1.eps; a.h1_out = p.h1; a.h1_stride = H;
         a.W1 = reinterpret_cast<const bf16_t*>(w.fc1_w); a.b1 = w.fc1_b; a.W2 = reinterpret_cast<const bf16_t*>(w.fc2_w); a.part = p.partF; a.part_stride = H;
-        a.st = e->d_st + r0; a.layer = l; a.ffn_gran = e->d_ffn_gran + r0 * c.ffn; a.err = e->d_chain_err;
+        a.st = p.st; a.layer = l; a.ffn_gran = p.ffn_gran; a.err = e->d_chain_err;
         // LayerNorm 2 in this launch's tail: the next layer starts from 16-bit rows.  Not for the last layer: the rows that feed lm_head are
         // normalised by rows_prologue_kernel (block-level sums: another order than the one-wave LayerNorm of the folded GEMMs)
         if (p.ln2_prev) {
-            a.b2 = w.fc2_b; a.ln2_g = w.ln2_g; a.ln2_b = w.ln2_b; a.y2_gran = e->d_rm_y2_gran + r0 * RM_Y2_GRANULES;
+            a.b2 = w.fc2_b; a.ln2_g = p.ln2(l).g; a.ln2_b = p.ln2(l).b; a.y2_gran = p.rm_y2_gran;
             a.x2_out = p.h0; a.x2_stride = H; a.xb_out = p.xb; a.xb_stride = H; a.part = nullptr;
             if (e->opt.rows_mlp_prefetch > 0 && e->opt.fuse_rows_attn) {
-                a.pf_k = reinterpret_cast<const bf16_t*>(e->kplane(rw.r0, l + 1)); a.pf_v = reinterpret_cast<const bf16_t*>(e->vplane(rw.r0, l + 1));
+                a.pf_k = reinterpret_cast<const bf16_t*>(p.kplane(l + 1)); a.pf_v = reinterpret_cast<const bf16_t*>(p.vplane(l + 1));
                 a.pf_row_stride = p.kv_row_elems; a.pf_max_seq = e->maxseq; a.pf_rounds = e->opt.rows_mlp_prefetch;
-                a.pf_wqkv = reinterpret_cast<const bf16_t*>(e->dl[l + 1].qkv_w); a.pf_sink = e->d_pf_sink;
+                a.pf_wqkv = reinterpret_cast<const bf16_t*>(p.w(l + 1).qkv_w); a.pf_sink = e->d_pf_sink;
             }
         }
-        a.trace = tm.trace_slot(4, 256);
-        launched(H16_CALL(e->hdt, HT, launch_rows_mlp<HT>(a, B, H, c.ffn, s)), "rows_mlp");
+        a.trace = p.tm.trace_slot(TK_FC1, 256);
+        launched(H16_CALL(e->hdt, HT, launch_rows_mlp<HT>(a, B, H, c.ffn, p.s)), "rows_mlp");
         return;
     }
     p.ln2_prev = false;
-    if (!p.rg.fold1) rows_prologue(e, s, PRO_LN, rw, in1, w.ln1_g, w.ln1_b, p.h1, tm);
+    if (!p.rg.fold1) p.rows_prologue(PRO_LN, in1, ln1, p.h1);
     {
         GemmDecArgs a{};
         a.W = reinterpret_cast<const bf16_t*>(w.fc1_w); a.bias = w.fc1_b; a.xb = p.xb; a.xb_stride = H; a.yb = p.ffb; a.yb_stride = c.ffn; a.N = c.ffn; a.K = H; a.B = B; a.ksplit = 1;
         a.act = ACT_RELU;
         if (p.rg.fold1) {
-            a.pin = in1.x; a.pin_stride = H; a.pin_parts = in1.nparts; a.pbias = in1.bias; a.pres = in1.res; a.pres_stride = H;
-            a.ln_g = w.ln1_g; a.ln_b = w.ln1_b; a.ln_eps = 1e-5f; a.xn_out = p.h1; a.xn_stride = H;
-            gemm_dec_ln(e, s, a, tm, 4);
-        } else gemm_dec(e, s, a, tm, 4);
+            p.fold_ln(a, in1, ln1, p.h1);
+            p.gemm_dec_ln(a, TK_FC1);
+        } else p.gemm_dec(a, TK_FC1);
     }
     // y2 = h1 + W2 f + b2
     GemmDecArgs a{};
     a.W = reinterpret_cast<const bf16_t*>(w.fc2_w); a.xb = p.ffb; a.xb_stride = c.ffn; a.N = H; a.K = c.ffn; a.B = B; a.ksplit = p.rg.ks_f; a.y_stride = H;
     if (p.rg.ks_f > 1) a.y = p.partF; else { a.y = p.y2; a.bias = w.fc2_b; a.res = p.h1; a.res_stride = H; }
-    gemm_dec(e, s, a, tm, 5);
+    p.gemm_dec(a, TK_FC2);
 }
 
 // The 24 OPT layers + lm_head of one decode step for a batch on the matrix cores (gemm_decode.hpp).  Same data flow as the
@@ -242,21 +289,19 @@ void mfma_mlp_half(MfmaStep& p, int l, ProIn in1) {
 // that its epilogue finishes y1: two launches fewer per layer
 // (the folded prologue reads its inputs once per block: 1 buffer in front of fc1, 4 split-K partials + residual in front of q/k/v, so
 //  the second stops paying earlier: profiles/r02_ab_batched_ln_fold.txt)
-void enqueue_layers_mfma(ma_engine* e, hipStream_t s, const float* x_embed, int len_override, StepTimer& tm, Rows rw) {
-    const ma_config& c = e->cfg;
-    const int H = c.hidden, L = c.layers;
-    const size_t r0 = rw.r0;
-    const RowsGates rg = rows_gates(e, rw.B, len_override);
-    MfmaStep p{e, s, tm, rw, len_override, rg, rg.fold1 ? 1 : gemm_dec_ksplit(H, H),
-               e->d_h0 + r0 * H, e->d_q + r0 * H, e->d_h1 + r0 * H, e->d_ypre1 + r0 * H, e->d_ypre2 + r0 * H, e->d_part + r0 * attn_workspace_floats(c.heads),
-               e->d_ks_o + 4 * r0 * H, e->d_ks_f + 4 * r0 * H, e->d_xb + r0 * H, e->d_ffb + r0 * c.ffn, e->kv_row_bytes / e->kv_elem};
+void mfma_chain(Step& p, const float* x_embed) {
+    ma_engine* e = p.e;
+    const int H = e->cfg.hidden, L = e->cfg.layers;
+    p.rg = rows_gates(e, p.rw.B, p.len_override);
+    p.ks_o = p.rg.fold1 ? 1 : gemm_dec_ksplit(H, H);
+    p.ln2_prev = false;
     for (int l = 0; l < L; ++l) mfma_mlp_half(p, l, mfma_attn_half(p, l, x_embed));
     // lm_head on LN2_{L-1}(y2)
-    if (!p.ln2_prev) rows_prologue(e, s, PRO_LN, rw, p.y2_of(L - 1), e->dl[L - 1].ln2_g, e->dl[L - 1].ln2_b, nullptr, tm);      // (else: the last MLP launch left xb)
+    if (!p.ln2_prev) p.rows_prologue(PRO_LN, p.y2_of(L - 1), p.ln2(L - 1), nullptr);      // (else: the last MLP launch left xb)
     GemmDecArgs g{};
-    g.W = reinterpret_cast<const bf16_t*>(e->P("transformer.lm_head.weight")); g.xb = p.xb; g.xb_stride = H;
-    g.y = e->d_logits + r0 * e->V; g.y_stride = e->V; g.N = e->V; g.K = H; g.B = rw.B; g.ksplit = 1;
-    gemm_dec(e, s, g, tm, 6);
+    g.W = reinterpret_cast<const bf16_t*>(e->decw.lm_head); g.xb = p.xb; g.xb_stride = H;
+    g.y = p.logits; g.y_stride = e->V; g.N = e->V; g.K = H; g.B = p.rw.B; g.ksplit = 1;
+    p.gemm_dec(g, TK_LMHEAD);
 }
 
 // The fused launches spin on granules written by other blocks of the same grid, so EVERY block of the grid (256 per batch row) must
@@ -272,99 +317,112 @@ bool fuse_qkv_attn(ma_engine* e, int B = 1, int len_override = -1) {
     return e->opt.fuse_qkv_attn && chain_fits(e, B, len_override) && e->cfg.hidden == 1024 && e->cfg.heads * 64 == e->cfg.hidden && e->cfg.layers <= 30;
 }
 
-// one OPT layer of one decode step.  `x_in` = this layer's input (row stride H) before its (optional) LayerNorm prologue.
-QkvAttnArgs make_qkv_attn_args(ma_engine* e, int l, const float* x_in, const float* ln_g, const float* ln_b, int len_override, Rows rw) {
-    const ma_config& c = e->cfg;
-    const int H = c.hidden; const size_t r0 = rw.r0;
-    const DecLayerPtrs& w = e->dl[l];
+// arguments of the two fused launches of layer l.  `x_in` = the layer's input (row stride H) before its (optional) LayerNorm prologue `ln`.
+QkvAttnArgs make_qkv_attn_args(const Step& p, int l, const float* x_in, const LnW& ln) {
+    ma_engine* e = p.e;
+    const int H = e->cfg.hidden;
+    const DecLayerPtrs& w = p.w(l);
     QkvAttnArgs a{};
-    a.W = reinterpret_cast<const bf16_t*>(w.qkv_w); a.bias = w.qkv_b; a.x = x_in; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f; a.xn_out = ln_g ? e->d_h0 + r0 * H : nullptr;
-    a.kcache = reinterpret_cast<bf16_t*>(e->kplane(rw.r0, l)); a.vcache = reinterpret_cast<bf16_t*>(e->vplane(rw.r0, l)); a.max_seq = e->maxseq; a.hidden = H;
-    a.st = e->d_st + r0; a.len_override = len_override; a.layer = l; a.ws = e->d_part + r0 * attn_workspace_floats(c.heads); a.gran = e->d_qkv_gran + r0 * 3 * H; a.err = e->d_chain_err;
-    a.x_stride = H; a.xn_stride = H; a.kv_row_stride = e->kv_row_bytes / e->kv_elem;
+    a.W = reinterpret_cast<const bf16_t*>(w.qkv_w); a.bias = w.qkv_b; a.x = x_in; a.ln_g = ln.g; a.ln_b = ln.b; a.ln_eps = ln.eps; a.xn_out = ln.g ? p.h0 : nullptr;
+    a.kcache = reinterpret_cast<bf16_t*>(p.kplane(l)); a.vcache = reinterpret_cast<bf16_t*>(p.vplane(l)); a.max_seq = e->maxseq; a.hidden = H;
+    a.st = p.st; a.len_override = p.len_override; a.layer = l; a.ws = p.part; a.gran = p.qkv_gran; a.err = e->d_chain_err;
+    a.x_stride = H; a.xn_stride = H; a.kv_row_stride = p.kv_row_elems;
     a.xcd_local = e->opt.qkv_xcd_local;
     return a;
 }
-OprojFc1Args make_oproj_fc1_args(ma_engine* e, int l, const float* resid, Rows rw, bool with_fc2) {
+OprojFc1Args make_oproj_fc1_args(const Step& p, int l, const float* resid, bool with_fc2) {
+    ma_engine* e = p.e;
     const ma_config& c = e->cfg;
-    const int H = c.hidden; const size_t r0 = rw.r0;
-    const DecLayerPtrs& w = e->dl[l];
+    const int H = c.hidden;
+    const DecLayerPtrs& w = p.w(l);
+    const LnW& ln1 = p.ln1(l);
     OprojFc1Args a{};
     a.Wo = reinterpret_cast<const bf16_t*>(w.o_w); a.bo = w.o_b; a.W1 = reinterpret_cast<const bf16_t*>(w.fc1_w); a.b1 = w.fc1_b;
-    a.ln_g = w.ln1_g; a.ln_b = w.ln1_b; a.ln_eps = 1e-5f; a.attn_ws = e->d_part + r0 * attn_workspace_floats(c.heads); a.heads = c.heads; a.res = resid;
-    a.h1_out = e->d_h1 + r0 * H; a.ffn_out = e->d_ffn + r0 * c.ffn;
-    a.st = e->d_st + r0; a.layer = l; a.gran = e->d_y1_gran + r0 * H; a.err = e->d_chain_err;
+    a.ln_g = ln1.g; a.ln_b = ln1.b; a.ln_eps = ln1.eps; a.attn_ws = p.part; a.heads = c.heads; a.res = resid;
+    a.h1_out = p.h1; a.ffn_out = p.ffn;
+    a.st = p.st; a.layer = l; a.gran = p.y1_gran; a.err = e->d_chain_err;
     a.res_stride = H; a.h1_stride = H; a.ffn_stride = c.ffn; a.sweep_waves = e->opt.oproj_fc1_sweep_waves;
-    if (with_fc2) { a.W2 = reinterpret_cast<const bf16_t*>(w.fc2_w); a.b2 = w.fc2_b; a.y2_out = e->d_ypre2 + r0 * H; a.y2_stride = H; a.gran2 = e->d_ffn_gran + r0 * c.ffn; }
+    if (with_fc2) { a.W2 = reinterpret_cast<const bf16_t*>(w.fc2_w); a.b2 = w.fc2_b; a.y2_out = p.y2; a.y2_stride = H; a.gran2 = p.ffn_gran; }
     return a;
 }
 
-// parts: 1 = the layer's first half (LayerNorm + q/k/v + attention), 2 = its second half (out_proj .. fc2), 3 = both
-void enqueue_layer(ma_engine* e, hipStream_t s, int l, const float* x_in, const float* ln_g, const float* ln_b, int len_override, StepTimer& tm, Rows rw, int parts = 3) {
+// First half of layer l on the GEMV chain: [LayerNorm `ln` of x_in +] q/k/v + attention.  Returns the residual that the second half adds.
+const float* gemv_attn_half(Step& p, int l, const float* x_in, const LnW& ln) {
+    ma_engine* e = p.e;
     const ma_config& c = e->cfg;
-    const int H = c.hidden, B = rw.B;
-    const size_t r0 = rw.r0;
-    const DecLayerPtrs& w = e->dl[l];
-    float* h0 = e->d_h0 + r0 * H; float* q = e->d_q + r0 * H; float* y1 = e->d_ypre1 + r0 * H; float* y2 = e->d_ypre2 + r0 * H;
-    float* h1 = e->d_h1 + r0 * H; float* ffn = e->d_ffn + r0 * c.ffn; float* part = e->d_part + r0 * attn_workspace_floats(c.heads);
-    const float* resid = ln_g ? h0 : x_in;
-    const size_t kv_row_elems = e->kv_row_bytes / e->kv_elem;
-    if (!(parts & 1)) {
-    } else if (fuse_qkv_attn(e, B, len_override)) {
+    const int H = c.hidden, B = p.rw.B;
+    const DecLayerPtrs& w = p.w(l);
+    const float* resid = ln.g ? p.h0 : x_in;
+    if (fuse_qkv_attn(e, B, p.len_override)) {
         // q, k, v projection + split-KV attention in one launch (qkv_attn.hpp): the exchange between them stays inside a head
-        QkvAttnArgs a = make_qkv_attn_args(e, l, x_in, ln_g, ln_b, len_override, rw);
-        a.trace = tm.trace_slot(2, ATTN_NCHUNK * c.heads);
-        if (tm.on(1)) {
-            launched(PREC_CALL(e->bf16, e->hdt, T, launch_qkv_attn<T>(a, c.heads, B, s)), "qkv_attn");
+        if (p.tm.on(CLS_ATTN)) {
+            QkvAttnArgs a = make_qkv_attn_args(p, l, x_in, ln);
+            a.trace = p.tm.trace_slot(TK_ATTN, ATTN_NCHUNK * c.heads);
+            launched(PREC_CALL(e->bf16, e->hdt, T, launch_qkv_attn<T>(a, c.heads, B, p.s)), "qkv_attn");
         }
-    } else {
-    {   // q,k,v = W h + b ; k,v appended to the cache in place ([3p] OPTAttention; 4.39.3 grows it with torch.cat)
-        GemvArgs a = gemv_base(e, rw);
-        a.W = w.qkv_w; a.bias = w.qkv_b; a.x = x_in; a.x_stride = H; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f; a.xn_out = ln_g ? h0 : nullptr; a.xn_stride = H;
-        a.y = q; a.y_stride = H; a.N = 3 * H; a.K = H; a.epi = EPI_QKV; a.kcache = e->kplane(rw.r0, l); a.vcache = e->vplane(rw.r0, l); a.kv_row_stride = kv_row_elems;
-        a.H = H; a.max_seq = e->maxseq;
-        a.trace = tm.trace_slot(1, gemv_blocks(e, a.N, a.K));
-        if (tm.on(0)) gemv(e, a, s, B);
+        return resid;
     }
-    if (tm.on(1)) {
-        unsigned long long* tr = tm.trace_slot(2, ATTN_NCHUNK * c.heads);
-        launched(PREC_CALL(e->bf16, e->hdt, T, launch_attn_decode<T>(q, e->kplane(rw.r0, l), e->vplane(rw.r0, l), c.heads, e->maxseq, e->d_st + r0, len_override, e->bf16 ? 1 : 0, part, s, tr, B, H, kv_row_elems)), "attn_decode");
+    // q,k,v = W h + b ; k,v appended to the cache in place ([3p] OPTAttention; 4.39.3 grows it with torch.cat)
+    GemvArgs a = p.gemv_args();
+    a.W = w.qkv_w; a.bias = w.qkv_b; a.x = x_in; a.x_stride = H; a.ln_g = ln.g; a.ln_b = ln.b; a.ln_eps = ln.eps; a.xn_out = ln.g ? p.h0 : nullptr; a.xn_stride = H;
+    a.y = p.q; a.y_stride = H; a.N = 3 * H; a.K = H; a.epi = EPI_QKV; a.kcache = p.kplane(l); a.vcache = p.vplane(l); a.kv_row_stride = p.kv_row_elems;
+    a.H = H; a.max_seq = e->maxseq;
+    p.gemv(a, TK_QKV);
+    if (p.tm.on(CLS_ATTN)) {
+        unsigned long long* tr = p.tm.trace_slot(TK_ATTN, ATTN_NCHUNK * c.heads);
+        launched(PREC_CALL(e->bf16, e->hdt, T, launch_attn_decode<T>(p.q, p.kplane(l), p.vplane(l), c.heads, e->maxseq, p.st, p.len_override, e->bf16 ? 1 : 0, p.part, p.s, tr, B, H, p.kv_row_elems)), "attn_decode");
     }
-    }
+    return resid;
+}
+
+// Second half of layer l on the GEMV chain: out_proj (+ merge of the attention partials) + LayerNorm 1 + fc1 + fc2 -> y2
+void gemv_mlp_half(Step& p, int l, const float* resid) {
+    ma_engine* e = p.e;
+    const ma_config& c = e->cfg;
+    const int H = c.hidden, B = p.rw.B;
+    const DecLayerPtrs& w = p.w(l);
+    const LnW& ln1 = p.ln1(l);
     bool fc2_done = false;
-    if (!(parts & 2)) return;
-    if (fuse_oproj_fc1(e, B, len_override)) {
+    if (fuse_oproj_fc1(e, B, p.len_override)) {
         // y1 = h + Wo a + bo; h1 = LN1(y1); f = relu(W1 h1 + b1) [; y2 = h1 + W2 f + b2] in one launch: y1 (and f) all-gathered inside it (oproj_fc1.hpp)
-        const bool with_fc2 = e->opt.fuse_fc2 != 0;
-        fc2_done = with_fc2;
-        OprojFc1Args a = make_oproj_fc1_args(e, l, resid, rw, with_fc2);
-        a.trace = tm.trace_slot(3, H / 4);
-        if (tm.on(0)) {
-            launched(PREC_CALL(e->bf16, e->hdt, T, launch_oproj_fc1<T>(a, H, c.ffn, B, s)), "oproj_fc1");
+        fc2_done = e->opt.fuse_fc2 != 0;
+        if (p.tm.on(CLS_WEIGHTS)) {
+            OprojFc1Args a = make_oproj_fc1_args(p, l, resid, fc2_done);
+            a.trace = p.tm.trace_slot(TK_OPROJ, H / 4);
+            launched(PREC_CALL(e->bf16, e->hdt, T, launch_oproj_fc1<T>(a, H, c.ffn, B, p.s)), "oproj_fc1");
         }
     } else {
-    {   // y1 = h + Wo a + bo  (LayerNorm deferred to the consumer's prologue)
-        GemvArgs a = gemv_base(e, rw);
-        // the attention output is never materialised: this GEMV's prologue merges the split-KV partials
-        a.W = w.o_w; a.bias = w.o_b; a.x = nullptr; a.attn_ws = part; a.attn_ws_stride = attn_workspace_floats(c.heads); a.attn_heads = c.heads;
-        a.res = resid; a.res_stride = H; a.y = y1; a.y_stride = H; a.N = H; a.K = H;
-        a.trace = tm.trace_slot(3, gemv_blocks(e, a.N, a.K));
-        if (tm.on(0)) gemv(e, a, s, B);
-    }
-    {   // f = relu(W1 LN1(y1) + b1); h1 = LN1(y1) kept for the residual
-        GemvArgs a = gemv_base(e, rw);
-        a.W = w.fc1_w; a.bias = w.fc1_b; a.x = y1; a.x_stride = H; a.ln_g = w.ln1_g; a.ln_b = w.ln1_b; a.ln_eps = 1e-5f; a.xn_out = h1; a.xn_stride = H;
-        a.y = ffn; a.y_stride = c.ffn; a.N = c.ffn; a.K = H; a.act = ACT_RELU;
-        a.trace = tm.trace_slot(4, gemv_blocks(e, a.N, a.K));
-        if (tm.on(0)) gemv(e, a, s, B);
-    }
+        {   // y1 = h + Wo a + bo  (LayerNorm deferred to the consumer's prologue)
+            GemvArgs a = p.gemv_args();
+            // the attention output is never materialised: this GEMV's prologue merges the split-KV partials
+            a.W = w.o_w; a.bias = w.o_b; a.x = nullptr; a.attn_ws = p.part; a.attn_ws_stride = attn_workspace_floats(c.heads); a.attn_heads = c.heads;
+            a.res = resid; a.res_stride = H; a.y = p.y1; a.y_stride = H; a.N = H; a.K = H;
+            p.gemv(a, TK_OPROJ);
+        }
+        {   // f = relu(W1 LN1(y1) + b1); h1 = LN1(y1) kept for the residual
+            GemvArgs a = p.gemv_args();
+            a.W = w.fc1_w; a.bias = w.fc1_b; a.x = p.y1; a.x_stride = H; a.ln_g = ln1.g; a.ln_b = ln1.b; a.ln_eps = ln1.eps; a.xn_out = p.h1; a.xn_stride = H;
+            a.y = p.ffn; a.y_stride = c.ffn; a.N = c.ffn; a.K = H; a.act = ACT_RELU;
+            p.gemv(a, TK_FC1);
+        }
     }
     if (!fc2_done) {   // y2 = h1 + W2 f + b2
-        GemvArgs a = gemv_base(e, rw);
-        a.W = w.fc2_w; a.bias = w.fc2_b; a.x = ffn; a.x_stride = c.ffn; a.res = h1; a.res_stride = H; a.y = y2; a.y_stride = H; a.N = H; a.K = c.ffn;
-        a.trace = tm.trace_slot(5, gemv_blocks(e, a.N, a.K));
-        if (tm.on(0)) gemv(e, a, s, B);
+        GemvArgs a = p.gemv_args();
+        a.W = w.fc2_w; a.bias = w.fc2_b; a.x = p.ffn; a.x_stride = c.ffn; a.res = p.h1; a.res_stride = H; a.y = p.y2; a.y_stride = H; a.N = H; a.K = c.ffn;
+        p.gemv(a, TK_FC2);
     }
+}
+
+// All layers [+ lm_head] of the GEMV chain from layer 0's input x0: layer l > 0 reads y2 of layer l - 1 through that layer's LayerNorm 2,
+// lm_head reads the last layer's the same way.  `layer(l, x_in, ln)` enqueues one layer.
+template <typename Layer>
+void gemv_chain_of(Step& p, const float* x0, Layer layer, bool head = true) {
+    const int L = p.e->cfg.layers;
+    for (int l = 0; l < L; ++l) layer(l, l == 0 ? x0 : p.y2, l == 0 ? NO_LN : p.ln2(l - 1));
+    if (head) p.lm_head(p.y2, p.H(), p.ln2(L - 1));
+}
+void gemv_chain(Step& p, const float* x0, bool head = true) {
+    gemv_chain_of(p, x0, [&](int l, const float* x_in, const LnW& ln) { gemv_mlp_half(p, l, gemv_attn_half(p, l, x_in, ln)); }, head);
 }
 
 
@@ -383,10 +441,10 @@ void ensure_embtab(ma_engine* e, hipStream_t s) {
     for (int v0 = 0; v0 < c.codebook_size; v0 += rows_per_launch) {
         GemvArgs a{};
         a.round_x = e->bf16 ? 1 : 0; a.act = ACT_NONE; a.epi = EPI_PLAIN;
-        a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias");
-        a.x = e->PF(DEC + "quantize_codebooks") + (size_t)v0 * c.codebook_dim; a.x_stride = c.codebook_dim;
+        a.W = e->decw.input_w; a.bias = e->decw.input_b;
+        a.x = e->decw.codebooks + (size_t)v0 * c.codebook_dim; a.x_stride = c.codebook_dim;
         a.y = e->d_embtab + (size_t)v0 * c.hidden; a.y_stride = c.hidden; a.N = c.hidden; a.K = c.codebook_dim;
-        gemv(e, a, s, std::min(rows_per_launch, c.codebook_size - v0));
+        gemv_launch(e, a, s, std::min(rows_per_launch, c.codebook_size - v0));
     }
     HIP_CHECK(hipStreamSynchronize(s));
     e->embtab_ready = true; e->embtab_small_rows = gemv_small_rows();
@@ -405,7 +463,6 @@ bool use_rows_fused(ma_engine*, int, int) { return false; }
 bool fuse_layer(ma_engine*, int = 1, int = -1) { return false; }
 bool persist_selected(ma_engine*, int, int) { return false; }
 void check_persist_error(ma_engine*, hipStream_t) {}
-void exp_reset_exchanges(ma_engine*, hipStream_t) {}
 void exp_alloc_exchanges(ma_engine*) {}
 int exp_layer_pair_occupancy() { return 1 << 20; }
 void exp_build_gates(ma_engine*, const hipDeviceProp_t&) {}
@@ -413,32 +470,22 @@ void exp_upload_layers(ma_engine*) {}
 void persist_trace(ma_engine*, int, uint64_t*, int32_t*, hipStream_t) { throw MaError(MA_ERR_STATE, "ma_persist_trace needs a library built with MA_EXPERIMENTAL=1"); }
 #endif
 
-void enqueue_lm_head(ma_engine* e, hipStream_t s, const float* x, int x_stride, const float* ln_g, const float* ln_b, StepTimer& tm, Rows rw) {
-    GemvArgs a = gemv_base(e, rw);
-    a.W = e->P("transformer.lm_head.weight"); a.x = x; a.x_stride = x_stride; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f;
-    a.y = e->d_logits + (size_t)rw.r0 * e->V; a.y_stride = e->V; a.N = e->V; a.K = e->cfg.hidden; a.epi = EPI_LMHEAD;
-    a.part_val = e->d_pval + (size_t)rw.r0 * e->V; a.part_idx = e->d_pidx + (size_t)rw.r0 * e->V; a.part_stride = e->V;
-    a.trace = tm.trace_slot(6, gemv_blocks(e, a.N, a.K));
-    if (tm.on(0)) gemv(e, a, s, rw.B);
-}
-
-void enqueue_pick(ma_engine* e, hipStream_t s, StepTimer& tm, Rows rw) {
-    if (!tm.on(3)) return;
-    const int nparts = (use_mfma_decode(e, rw.B) && !use_rows_fused(e, rw.B, -1)) ? 0 : e->n_parts;
+void enqueue_pick(Step& p) {
+    ma_engine* e = p.e;
+    if (!p.tm.on(CLS_PICK)) return;
+    const int B = p.rw.B;
+    const int nparts = (use_mfma_decode(e, B) && !use_rows_fused(e, B, -1)) ? 0 : e->n_parts;
     PickEmbed em{};
-    const bool emb = embed_from_table(e, rw.B);
+    const bool emb = embed_from_table(e, B);
     if (emb) {
         // (a captured step cannot build the table: generate / profile / trace call ensure_embtab before they capture or enqueue)
         if (!e->embtab_ready) throw MaError(MA_ERR_STATE, "internal: decode step enqueued before the embedding table was built");
-        const int H = e->cfg.hidden;
-        em.table = e->d_embtab; em.extra = e->PF(DEC + "extra_embeds.weight"); em.tokpos = e->PF(DEC + "token_embed_positions.weight");
-        em.cond = e->PF(DEC + "cond_embed.weight"); em.postab = e->PF(DEC + "embed_positions.weight"); em.pos_rows = e->entry(DEC + "embed_positions.weight").rows;
-        em.e_out = e->d_e + (size_t)rw.r0 * H; em.e_stride = H; em.H = H;
+        const DecW& d = e->decw;
+        em.table = e->d_embtab; em.extra = d.extra; em.tokpos = d.tokpos; em.cond = d.cond; em.postab = d.postab; em.pos_rows = d.pos_rows;
+        em.e_out = p.de; em.e_stride = p.H(); em.H = p.H();
     }
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(rw.B), dim3(256), (size_t)e->V * sizeof(float), s, e->d_logits + (size_t)rw.r0 * e->V, e->V,
-                           e->d_pval + (size_t)rw.r0 * e->V, e->d_pidx + (size_t)rw.r0 * e->V, nparts, e->V, e->d_st + rw.r0,
-                           e->w_tokens + (size_t)rw.r0 * e->maxnew, e->maxnew, e->T, em);
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(256), (size_t)e->V * sizeof(float), p.s, p.logits, e->V, p.pval, p.pidx, nparts, e->V, p.st, p.w_tokens, e->maxnew, e->T, em);
     };
     if (emb) launch(pick_kernel<true>); else launch(pick_kernel<false>);
     HIP_CHECK(hipGetLastError());
@@ -457,73 +504,47 @@ void check_chain_error(ma_engine* e, hipStream_t s) {
 
 // The embedding launch: e = (extra[tok] | input_layer(codebook[tok - 3]) + bias) + the three positional rows, for the token and step in DecState.
 // The first launch of every step without embed_table; with it, only behind a state that no pick produced (state_at, engine_generate.hpp).
-GemvArgs make_embed_args(ma_engine* e, Rows rw) {
-    const ma_config& c = e->cfg;
-    const int H = c.hidden;
-    GemvArgs a = gemv_base(e, rw);
-    a.W = e->P(DEC + "input_layer.weight"); a.bias = e->PF(DEC + "input_layer.bias"); a.y = e->d_e + (size_t)rw.r0 * H; a.y_stride = H; a.N = H; a.K = c.codebook_dim;
-    a.epi = EPI_EMBED; a.codebook = e->PF(DEC + "quantize_codebooks"); a.extra = e->PF(DEC + "extra_embeds.weight");
-    a.tokpos = e->PF(DEC + "token_embed_positions.weight"); a.cond = e->PF(DEC + "cond_embed.weight");
-    a.postab = e->PF(DEC + "embed_positions.weight"); a.T = e->T;
+GemvArgs make_embed_args(const Step& p) {
+    ma_engine* e = p.e;
+    const DecW& d = e->decw;
+    const int H = p.H();
+    GemvArgs a = p.gemv_args();
+    a.W = d.input_w; a.bias = d.input_b; a.y = p.de; a.y_stride = H; a.N = H; a.K = e->cfg.codebook_dim;
+    a.epi = EPI_EMBED; a.codebook = d.codebooks; a.extra = d.extra; a.tokpos = d.tokpos; a.cond = d.cond; a.postab = d.postab; a.T = e->T;
     // batched matrix-core step: the embedding launch also leaves the 16-bit operand of layer 0's q/k/v GEMM (no prologue launch for it)
-    if (use_mfma_decode(e, rw.B)) { a.yb = e->d_xb + (size_t)rw.r0 * H; a.yb_stride = H; }
+    if (use_mfma_decode(e, p.rw.B)) { a.yb = p.xb; a.yb_stride = H; }
     return a;
 }
-void enqueue_embed(ma_engine* e, hipStream_t s, StepTimer& tm, Rows rw) {
-    GemvArgs a = make_embed_args(e, rw);
-    a.trace = tm.trace_slot(0, gemv_blocks(e, a.N, a.K));
-    if (tm.on(0)) gemv(e, a, s, rw.B);
-}
+void enqueue_embed(Step& p) { p.gemv(make_embed_args(p), TK_EMBED); }
 
-// One full decode step (shape_opt.py:318-328 embedding branch -> 24 layers -> lm_head -> pick) for rows r0..r0+B-1.
+// One full decode step (shape_opt.py:318-328 embedding branch -> 24 layers -> lm_head -> pick) for the rows of `p`.
 // Replayable: no host-side step-dependent argument.
-void enqueue_decode_step(ma_engine* e, hipStream_t s, int len_override, StepTimer& tm, Rows rw = Rows{}, int impl = 0) {
+void enqueue_decode_step(Step& p, int impl = 0) {
+    ma_engine* e = p.e;
 #ifdef MA_EXPERIMENTAL
-    if (impl == 1) { enqueue_persist_step(e, s, tm); return; }
+    if (impl == 1) { enqueue_persist_step(p); return; }
 #else
     if (impl != 0) throw MaError(MA_ERR_STATE, "the persistent decode step is not part of this build (MA_EXPERIMENTAL)");
 #endif
-    const ma_config& c = e->cfg;
-    const int H = c.hidden;
-    float* de = e->d_e + (size_t)rw.r0 * H;
+    const int B = p.rw.B;
     // embed_table: the previous pick (or enqueue_embed behind a state set by hand) left this step's layer-0 input in `de`
-    if (!embed_from_table(e, rw.B)) enqueue_embed(e, s, tm, rw);
+    if (!embed_from_table(e, B)) enqueue_embed(p);
 #ifdef MA_EXPERIMENTAL
-    if (use_rows_fused(e, rw.B, len_override)) {
-        const float* y2 = e->d_ypre2 + (size_t)rw.r0 * H;
-        for (int l = 0; l < c.layers; ++l) {
-            if (l == 0) enqueue_layer_rows_fused(e, s, 0, de, nullptr, nullptr, tm, rw);
-            else enqueue_layer_rows_fused(e, s, l, y2, e->dl[l - 1].ln2_g, e->dl[l - 1].ln2_b, tm, rw);
-        }
-        enqueue_lm_head(e, s, y2, H, e->dl[c.layers - 1].ln2_g, e->dl[c.layers - 1].ln2_b, tm, rw);
-    } else
+    if (use_rows_fused(e, B, p.len_override)) gemv_chain_of(p, p.de, [&](int l, const float* x_in, const LnW& ln) { enqueue_layer_rows_fused(p, l, x_in, ln); });
+    else if (!use_mfma_decode(e, B) && fuse_layer(e, B, p.len_override) && e->cfg.layers >= 2) enqueue_layer_pairs(p);
+    else
 #endif
-    if (use_mfma_decode(e, rw.B)) {
-        enqueue_layers_mfma(e, s, de, len_override, tm, rw);
-    } else {
-        const float* y2 = e->d_ypre2 + (size_t)rw.r0 * H;
-#ifdef MA_EXPERIMENTAL
-        if (fuse_layer(e, rw.B, len_override) && c.layers >= 2) {
-            // first half of layer 0 | (second half of l + first half of l + 1) x (L - 1) | second half of layer L - 1
-            const float* h0 = e->d_h0 + (size_t)rw.r0 * H;
-            enqueue_layer(e, s, 0, de, nullptr, nullptr, len_override, tm, rw, 1);
-            for (int l = 0; l + 1 < c.layers; ++l) enqueue_layer_pair(e, s, l, l == 0 ? de : h0, len_override, tm, rw);
-            enqueue_layer(e, s, c.layers - 1, y2, e->dl[c.layers - 2].ln2_g, e->dl[c.layers - 2].ln2_b, len_override, tm, rw, 2);
-        } else
-#endif
-        for (int l = 0; l < c.layers; ++l) {
-            if (l == 0) enqueue_layer(e, s, 0, de, nullptr, nullptr, len_override, tm, rw);
-            else enqueue_layer(e, s, l, y2, e->dl[l - 1].ln2_g, e->dl[l - 1].ln2_b, len_override, tm, rw);
-        }
-        enqueue_lm_head(e, s, y2, H, e->dl[c.layers - 1].ln2_g, e->dl[c.layers - 1].ln2_b, tm, rw);
-    }
-    enqueue_pick(e, s, tm, rw);
+    if (use_mfma_decode(e, B)) mfma_chain(p, p.de);
+    else gemv_chain(p, p.de);
+    enqueue_pick(p);
 }
 
 void drop_graphs(ma_engine* e) {
-    for (auto& kv : e->gexec) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    for (auto& kv : e->graph) if (kv.second) (void)hipGraphDestroy(kv.second);
-    e->gexec.clear(); e->graph.clear();
+    for (auto& kv : e->graphs) {
+        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
+    }
+    e->graphs.clear();
 }
 
 // ---- row groups ------------------------------------------------------------------------------------------------------------
@@ -558,35 +579,34 @@ void ensure_group_streams(ma_engine* e, size_t G) {
 }
 
 // one captured step per row range (the grids depend on B, the pointers on r0) and step implementation
-int graph_key(Rows rw, int impl) { return rw.B + 1000 * impl + 10000 * rw.r0; }
+StepGraphKey graph_key(Rows rw, int impl) { return StepGraphKey{rw.r0, rw.B, impl}; }
 void ensure_graph(ma_engine* e, Rows rw, int impl = 0) {
-    const int key = graph_key(rw, impl);
-    if (!e->cfg.use_graph || e->gexec.count(key)) return;
+    if (!e->cfg.use_graph || e->graphs.count(graph_key(rw, impl))) return;
     StepTimer none;
     if (!e->cap_stream) HIP_CHECK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
     hipStream_t s = e->cap_stream;
-    hipGraph_t g = nullptr;
+    Step p(e, s, none, rw);
+    StepGraph g;
     HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     try {
-        enqueue_decode_step(e, s, -1, none, rw, impl);
+        enqueue_decode_step(p, impl);
     } catch (...) {
-        (void)hipStreamEndCapture(s, &g);
-        if (g) (void)hipGraphDestroy(g);
+        (void)hipStreamEndCapture(s, &g.graph);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
         throw;
     }
-    HIP_CHECK(hipStreamEndCapture(s, &g));
-    hipGraphExec_t ge = nullptr;
-    hipError_t r = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    if (r != hipSuccess) { (void)hipGraphDestroy(g); HIP_CHECK(r); }
-    e->graph[key] = g; e->gexec[key] = ge;
+    HIP_CHECK(hipStreamEndCapture(s, &g.graph));
+    hipError_t r = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+    if (r != hipSuccess) { (void)hipGraphDestroy(g.graph); HIP_CHECK(r); }
+    e->graphs[graph_key(rw, impl)] = g;
 }
 void ensure_graphs(ma_engine* e, int B, int impl = 0) {
     for (const Rows& rw : decode_groups(e, B, impl)) ensure_graph(e, rw, impl);
 }
 
 void launch_step(ma_engine* e, hipStream_t s, Rows rw, int impl = 0) {
-    if (e->cfg.use_graph) HIP_CHECK(hipGraphLaunch(e->gexec.at(graph_key(rw, impl)), s));
-    else { StepTimer none; enqueue_decode_step(e, s, -1, none, rw, impl); }
+    if (e->cfg.use_graph) HIP_CHECK(hipGraphLaunch(e->graphs.at(graph_key(rw, impl)).exec, s));
+    else { StepTimer none; Step p(e, s, none, rw); enqueue_decode_step(p, impl); }
 }
 
 // n decode steps of rows 0..B-1, ordered after what is on `s` and before what comes next on it

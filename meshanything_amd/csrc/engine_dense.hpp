@@ -216,16 +216,12 @@ void prefill(const Dense& d, const float* prefix, int row0, int B) {
     if (e->opt.prefill_stepwise) {
         // debug path: feed the prefix rows through the decode-step kernels one position at a time, one sample at a time
         for (int b = 0; b < B; ++b) {
-            const Rows rw{row0 + b, 1};
+            Step p(e, s, none, Rows{row0 + b, 1});
             for (int j = 0; j < T; ++j) {
-                hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, s, e->d_st + row0 + b, 0, j, 0, 1);
+                hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, s, p.st, 0, j, 0, 1);
                 HIP_CHECK(hipGetLastError());
-                for (int l = 0; l < c.layers; ++l) {
-                    if (l == 0) enqueue_layer(e, s, 0, h + ((size_t)b * T + j) * H, nullptr, nullptr, -1, none, rw);
-                    else enqueue_layer(e, s, l, e->d_ypre2 + (size_t)(row0 + b) * H, e->dl[l - 1].ln2_g, e->dl[l - 1].ln2_b, -1, none, rw);
-                }
+                gemv_chain(p, h + ((size_t)b * T + j) * H, j == T - 1);          // (lm_head behind the last position only)
             }
-            enqueue_lm_head(e, s, e->d_ypre2 + (size_t)(row0 + b) * H, H, e->dl[c.layers - 1].ln2_g, e->dl[c.layers - 1].ln2_b, none, rw);
         }
         return;
     }
@@ -321,7 +317,7 @@ void prefill(const Dense& d, const float* prefix, int row0, int B) {
         HIP_CHECK(hipStreamWaitEvent(s, e->tail_join, 0));
     }
     // only the last prefix row of every sample feeds lm_head (the reference computes all 257 rows and discards 256, shape_opt.py:155)
-    enqueue_lm_head(e, s, h + (size_t)(T - 1) * H, T * H, nullptr, nullptr, none, Rows{row0, B});
+    Step(e, s, none, Rows{row0, B}).lm_head(h + (size_t)(T - 1) * H, T * H, NO_LN);
 }
 
 // ------------------------------------------------------------------------------------------------ detokenizer

@@ -1,4 +1,4 @@
-// generate(): state records, prefill, bursts of decode steps, and the fall-back when an in-launch exchange times out. (No includes of its own: compiled only inside engine.hip, in its include order.)
+// generate(): state records and the per-generation reset of the exchange buffers (e->exchanges), prefill, bursts of decode steps, and the fall-back when an in-launch exchange times out. (No includes of its own: compiled only inside engine.hip, in its include order.)
 #pragma once
 
 namespace {
@@ -12,18 +12,9 @@ void init_state(ma_engine* e, hipStream_t s, const ma_sample_cfg& sc, int B, int
     st.forced = reinterpret_cast<const long long*>(sc.forced_tokens); st.logits_out = sc.logits_out; st.logits_first = sc.logits_out ? sc.logits_first_step : 0;
     hipLaunchKernelGGL(init_state_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, s, e->d_st, st, B, e->V);
     HIP_CHECK(hipGetLastError());
-    // a word left raised by a call that threw before reading it must not make this generation's sweeps give up early
-    HIP_CHECK(hipMemsetAsync(e->d_chain_err, 0, sizeof(unsigned), s));
-    // the fused q/k/v + attention launch tags its exchange with the cache position, which restarts here
-    HIP_CHECK(hipMemsetAsync(e->d_qkv_gran, 0, (size_t)e->cfg.max_batch * 3 * e->cfg.hidden * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_y1_gran, 0, (size_t)e->cfg.max_batch * e->cfg.hidden * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_ffn_gran, 0, (size_t)e->cfg.max_batch * e->cfg.ffn * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_attn_pair_gran, 0, (size_t)e->cfg.max_batch * e->cfg.heads * ATTN_PAIR_GRANULES * sizeof(unsigned long long), s));
-    HIP_CHECK(hipMemsetAsync(e->d_y2_gran, 0, (size_t)e->cfg.max_batch * e->cfg.hidden * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_ra_qkv_gran, 0, (size_t)e->cfg.max_batch * RA_QKV_GRANULES * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_ra_out_gran, 0, (size_t)e->cfg.max_batch * RA_OUT_GRANULES * sizeof(u64), s));
-    HIP_CHECK(hipMemsetAsync(e->d_rm_y2_gran, 0, (size_t)e->cfg.max_batch * RM_Y2_GRANULES * sizeof(u64), s));
-    exp_reset_exchanges(e, s);
+    // the fused launches tag their in-launch exchanges with the cache position, which restarts here; and an error word left raised by a call that
+    // threw before reading it must not make this generation's sweeps give up early (e->exchanges: filled by xalloc, engine_state.hpp)
+    for (const Exchange& x : e->exchanges) HIP_CHECK(hipMemsetAsync(x.p, 0, x.reset_bytes, s));
 }
 
 ma_sample_cfg resolve_sample_cfg(ma_engine* e, const ma_sample_cfg* sc) {
@@ -55,7 +46,7 @@ void state_at(ma_engine* e, hipStream_t s, int B, int kv_len) {
     HIP_CHECK(hipGetLastError());
     // embed_table: no pick produced this state, so nothing wrote the layer-0 input of the step that follows: one embedding launch does
     // (ma_profile_decode, ma_trace_decode, ma_persist_trace all come through here; generate()'s first step is fed by the pick after the prefill)
-    if (embed_from_table(e, B)) { StepTimer none; enqueue_embed(e, s, none, Rows{0, B}); }
+    if (embed_from_table(e, B)) { StepTimer none; Step p(e, s, none, Rows{0, B}); enqueue_embed(p); }
 }
 
 // generate() for a batch of B rows: every row is prefilled, then all rows step together (they share the weight stream and
@@ -84,7 +75,8 @@ int generate_batch_once(ma_engine* e, hipStream_t s, const float* prefix, int B,
     if (e->opt.prefill_stepwise) init_state(e, s, sc, B, maxn);         // the stepwise prefill used the state's pos field
     StepTimer none;
     // token 0 (expected bos; dropped later, meshanything.py:166); embed_table: this pick also writes the first decode step's layer-0 input
-    enqueue_pick(e, s, none, Rows{0, B});
+    Step all_rows(e, s, none, Rows{0, B});
+    enqueue_pick(all_rows);
     int produced = 1;
     bool finished = false;
     while (produced < maxn && !finished) {

@@ -1,4 +1,4 @@
-// Shared state of the host side: error types, the precision-dispatch macros, and the engine record (struct ma_engine). (No includes of its own: compiled only inside engine.hip, in its include order.)
+// Shared state of the host side: error types, the precision-dispatch macros, the resolved weight records (DenseW, DecW), and the engine record (struct ma_engine) with its exchange table and captured steps. (No includes of its own: compiled only inside engine.hip, in its include order.)
 #pragma once
 
 namespace {
@@ -91,6 +91,17 @@ struct DenseW {
     const float *cond_embed, *embed_pos; std::vector<PostLnLayerW> opt;                                       // prefill
     Lin tok_cond_head, tok_cond, project_down, to_coor; LnW point_ln, face_ln; const float *point_pe, *pos_emb, *codebooks; std::vector<PostLnLayerW> bert;      // detokenizer
 };
+// ... and what the decode step reads besides its layers (e->dl; LayerNorms: dw.opt[l].ln1 / ln2): resolved by the same function
+struct DecW {
+    const void *lm_head, *input_w; const float* input_b;                       // lm_head and input_layer matrices in the policy dtype
+    const float *codebooks, *extra, *tokpos, *cond, *postab; int pos_rows;      // quantize_codebooks, extra_embeds, token_embed_positions, cond_embed, embed_positions and its rows
+};
+
+// A buffer through which blocks of one launch hand data to each other (granules: common.hpp), with the bytes that every generation starts from zero
+struct Exchange { void* p; size_t reset_bytes; };
+// one captured decode step, by (first row, rows, step implementation): the grids depend on the rows, the pointers on the first row
+struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
+typedef std::tuple<int, int, int> StepGraphKey;
 
 struct ma_engine {
     ma_config cfg{};
@@ -181,8 +192,10 @@ struct ma_engine {
     u64* d_gran = nullptr; unsigned* d_serial = nullptr; unsigned* d_err = nullptr; unsigned* h_err = nullptr;
     u64* d_ptrace = nullptr;
 
-    // ---- exchange buffers of the launches that hand data over inside a launch (granules: common.hpp)
-    u64* d_qkv_gran = nullptr;       // fused q/k/v + attention: [max_batch][3 hidden]
+    // ---- exchange buffers of the launches that hand data over inside a launch (granules: common.hpp): each allocated by xalloc, which
+    // zeroes it and lists what init_state (engine_generate.hpp) zeroes again for every generation
+    std::vector<Exchange> exchanges;
+    u64* d_qkv_gran = nullptr;     // fused q/k/v + attention: [max_batch][3 hidden]
     u64* d_y1_gran = nullptr;        // fused out_proj + fc1: [max_batch][hidden]
     u64* d_y2_gran = nullptr;        // [max_batch][hidden] (y2 handed to the next layer inside a launch)
     u64* d_ffn_gran = nullptr;       // [max_batch][ffn] (fc2 in the out_proj + fc1 launch; relu(fc1) of rows_mlp.hpp)
@@ -190,8 +203,8 @@ struct ma_engine {
     u64 *d_ra_qkv_gran = nullptr, *d_ra_out_gran = nullptr;      // rows_attn.hpp: [max_batch][RA_QKV_GRANULES], [max_batch][RA_OUT_GRANULES]
     u64* d_rm_y2_gran = nullptr;     // rows_mlp.hpp step E: [max_batch][RM_Y2_GRANULES]
     u64* d_part_gran = nullptr;      // rows_fused.hpp (MA_EXPERIMENTAL): [max_batch][heads][16][66], its in-launch split-KV partial exchange
-    u64* d_ln_gran = nullptr; size_t ln_gran_tiles = 0; unsigned ln_epoch = 0;      // gemm256.hpp LNF form (fuse_ln)
-    unsigned* d_chain_err = nullptr; unsigned* h_chain_err = nullptr;               // error word + counters of all of them (build_engine)
+    u64* d_ln_gran = nullptr; size_t ln_gran_tiles = 0; unsigned ln_epoch = 0;      // gemm256.hpp LNF form (fuse_ln); its epochs run on across generations: never reset
+    unsigned* d_chain_err = nullptr; unsigned* h_chain_err = nullptr;               // error word (reset per generation) + counters (never) of all of them (build_engine)
 
     // ---- dense-phase workspace: dense_rows samples stacked along the rows.  w_* / p_*: fp32 streams; a_*: activation tensors
     // (dense_ops.hpp: 2-byte elements in a 16-bit phase, 4 in an exact one; every phase entry says which in its Dense context, engine_dense.hpp).
@@ -200,6 +213,7 @@ struct ma_engine {
     // the detokenizer's BERT stack follow the policy dtype.
     bool enc_exact = false;          // encoder weights are fp32 arena entries and the encoder's activations fp32 (always true under the fp32 policy)
     DenseW dw;                       // the dense phases' weights
+    DecW decw;                       // the decode step's
     float *w_data = nullptr, *w_lat = nullptr, *w_lat2 = nullptr, *w_pf = nullptr, *w_x = nullptr, *w_y = nullptr, *w_fe = nullptr, *w_logit = nullptr;
     float *p_h = nullptr, *p_y = nullptr;
     long p_y_part_stride = 0;        // p_y holds up to 4 partial sums of a GEMM split along K (gemm256.hpp GemmSplitK), this many floats apart, for the small prefills that use it
@@ -212,8 +226,7 @@ struct ma_engine {
     long long *w_tokens = nullptr, *w_ids = nullptr;
 
     // ---- streams, events, graphs
-    std::map<int, hipGraph_t> graph;           // one captured decode step per batch size
-    std::map<int, hipGraphExec_t> gexec;
+    std::map<StepGraphKey, StepGraph> graphs;
     hipStream_t cap_stream = nullptr;   // capture happens on a private stream (the caller's may be the legacy null stream)
     // row groups of a batched step (decode_groups): group g steps its rows on grp_stream[g], forked from / joined to the caller's stream
     std::vector<hipStream_t> grp_stream; std::vector<hipEvent_t> grp_done; hipEvent_t grp_fork = nullptr;
@@ -230,6 +243,13 @@ struct ma_engine {
         HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(Tp)));
         allocs.push_back(p);
         return reinterpret_cast<Tp*>(p);
+    }
+    // an exchange buffer of n elements, zeroed; its first n_reset elements (default: all, 0: none) are zeroed again for every generation
+    template <typename Tp> Tp* xalloc(size_t n, size_t n_reset = ~size_t(0)) {
+        Tp* p = dmalloc<Tp>(n);
+        HIP_CHECK(hipMemset(p, 0, n * sizeof(Tp)));
+        if (n_reset) exchanges.push_back(Exchange{p, std::min(n, n_reset) * sizeof(Tp)});
+        return p;
     }
     const Entry& entry(const std::string& name) const {
         auto it = L.entry_by_name.find(name);

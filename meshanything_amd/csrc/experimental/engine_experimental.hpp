@@ -1,6 +1,7 @@
 // Host side of the measured-and-rejected decode-step forms (MA_EXPERIMENTAL=1 libraries only): the rows-looped two-launch layer
 // (rows_fused.hpp), the layer-pair launch (layer_fused.hpp) and the persistent one-launch step (persist.hpp).  Included by
-// engine_decode.hpp, which gives the product build one block of stubs instead; no includes of its own.
+// engine_decode.hpp, which gives the product build one block of stubs instead; no includes of its own.  Like the product chains, every enqueue
+// function takes the Step context of engine_decode.hpp and builds on its layer halves and argument makers.
 #pragma once
 
 namespace {
@@ -15,39 +16,41 @@ bool use_rows_fused(ma_engine* e, int B, int len_override) {
            c.hidden == 1024 && c.ffn == 4096 && c.heads * 64 == c.hidden && c.heads * ATTN_NCHUNK == 256 && c.layers <= 30;
 }
 
-void enqueue_layer_rows_fused(ma_engine* e, hipStream_t s, int l, const float* x_in, const float* ln_g, const float* ln_b, StepTimer& tm, Rows rw) {
-    const ma_config& c = e->cfg;
+// one layer as two launches that share ONE argument record: both trace slots are taken before either launch (a trace never runs with a filter)
+void enqueue_layer_rows_fused(Step& p, int l, const float* x_in, const LnW& ln) {
+    const ma_config& c = p.e->cfg;
     const int H = c.hidden;
-    const size_t r0 = rw.r0;
     RowsFusedArgs A{};
-    A.q = make_qkv_attn_args(e, l, x_in, ln_g, ln_b, -1, rw);
-    A.q.trace = tm.trace_slot(2, ATTN_NCHUNK * c.heads);
-    const float* resid = ln_g ? e->d_h0 + r0 * H : x_in;
-    A.o = make_oproj_fc1_args(e, l, resid, rw, true);
-    A.o.trace = tm.trace_slot(3, H / 4);
-    A.part_gran = e->d_part_gran + r0 * c.heads * ATTN_NCHUNK * RF_PART;
-    A.attn_out = e->d_xb + r0 * H; A.attn_out_stride = H;
-    A.B = rw.B;
-    if (tm.on(1)) {
-        launched(launch_qkv_attn_rows(A, c.heads, s), "qkv_attn_rows");
-    }
-    if (tm.on(0)) {
-        launched(launch_oproj_fc1_rows(A, H, c.ffn, s), "oproj_fc1_rows");
-    }
+    A.q = make_qkv_attn_args(p, l, x_in, ln);
+    A.q.trace = p.tm.trace_slot(TK_ATTN, ATTN_NCHUNK * c.heads);
+    A.o = make_oproj_fc1_args(p, l, ln.g ? p.h0 : x_in, true);
+    A.o.trace = p.tm.trace_slot(TK_OPROJ, H / 4);
+    A.part_gran = p.part_gran;
+    A.attn_out = p.xb; A.attn_out_stride = H;
+    A.B = p.rw.B;
+    if (p.tm.on(CLS_ATTN)) launched(launch_qkv_attn_rows(A, c.heads, p.s), "qkv_attn_rows");
+    if (p.tm.on(CLS_WEIGHTS)) launched(launch_oproj_fc1_rows(A, H, c.ffn, p.s), "oproj_fc1_rows");
 }
 
 bool fuse_layer(ma_engine* e, int B = 1, int len_override = -1) { return e->opt.fuse_layer && e->bf16 && e->hdt == MA_DTYPE_BF16 && fuse_qkv_attn(e, B, len_override) && fuse_oproj_fc1(e, B, len_override) && e->opt.fuse_fc2; }
 
-// second half of layer l + first half of layer l + 1 in one launch (layer_fused.hpp); belongs to the "cache" class of the profiler
-void enqueue_layer_pair(ma_engine* e, hipStream_t s, int l, const float* resid, int len_override, StepTimer& tm, Rows rw) {
-    const ma_config& c = e->cfg;
+// second half of layer l + first half of layer l + 1 in one launch (layer_fused.hpp); belongs to the attention class of the profiler
+void enqueue_layer_pair(Step& p, int l, const float* resid) {
+    const ma_config& c = p.e->cfg;
+    if (!p.tm.on(CLS_ATTN)) return;
     LayerFusedArgs a{};
-    a.o = make_oproj_fc1_args(e, l, resid, rw, true);
-    a.q = make_qkv_attn_args(e, l + 1, nullptr, e->dl[l].ln2_g, e->dl[l].ln2_b, len_override, rw);
-    a.gran3 = e->d_y2_gran + (size_t)rw.r0 * c.hidden;
-    if (tm.on(1)) {
-        launched(launch_layer_fused(a, c.hidden, c.ffn, c.heads, rw.B, s), "layer_fused");
-    }
+    a.o = make_oproj_fc1_args(p, l, resid, true);
+    a.q = make_qkv_attn_args(p, l + 1, nullptr, p.ln2(l));
+    a.gran3 = p.y2_gran;
+    launched(launch_layer_fused(a, c.hidden, c.ffn, c.heads, p.rw.B, p.s), "layer_fused");
+}
+// first half of layer 0 | (second half of l + first half of l + 1) x (L - 1) | second half of layer L - 1 | lm_head
+void enqueue_layer_pairs(Step& p) {
+    const int L = p.e->cfg.layers;
+    gemv_attn_half(p, 0, p.de, NO_LN);
+    for (int l = 0; l + 1 < L; ++l) enqueue_layer_pair(p, l, l == 0 ? p.de : p.h0);
+    gemv_mlp_half(p, L - 1, p.h0);
+    p.lm_head(p.y2, p.H(), p.ln2(L - 1));
 }
 
 // ---- persistent decode step (persist.hpp) ----------------------------------------------------------------------------------
@@ -55,18 +58,18 @@ void enqueue_layer_pair(ma_engine* e, hipStream_t s, int l, const float* resid, 
 bool persist_eligible(ma_engine* e, int B, int do_sample) { return e->persist_shape && B == 1 && !do_sample; }
 bool persist_selected(ma_engine* e, int B, int do_sample) { return e->opt.decode_impl == 1 && persist_eligible(e, B, do_sample); }
 
-void enqueue_persist_step(ma_engine* e, hipStream_t s, StepTimer& tm, u64* trace = nullptr) {
-    if (!tm.on(2)) return;
-    const ma_config& c = e->cfg;
+void enqueue_persist_step(Step& p, u64* trace = nullptr) {
+    ma_engine* e = p.e;
+    if (!p.tm.on(CLS_PERSIST)) return;
+    const DecW& d = e->decw;
     PersistArgs a{};
-    a.layers = e->d_layers; a.L = c.layers;
-    a.lm_head = reinterpret_cast<const bf16_t*>(e->P("transformer.lm_head.weight")); a.V = e->V;
-    a.embtab = e->d_embtab; a.extra = e->PF(DEC + "extra_embeds.weight"); a.tokpos = e->PF(DEC + "token_embed_positions.weight");
-    a.cond = e->PF(DEC + "cond_embed.weight"); a.postab = e->PF(DEC + "embed_positions.weight"); a.T = e->T;
+    a.layers = e->d_layers; a.L = e->cfg.layers;
+    a.lm_head = reinterpret_cast<const bf16_t*>(d.lm_head); a.V = e->V;
+    a.embtab = e->d_embtab; a.extra = d.extra; a.tokpos = d.tokpos; a.cond = d.cond; a.postab = d.postab; a.T = e->T;
     a.kv = reinterpret_cast<bf16_t*>(e->kv); a.kv_plane = e->kv_plane / e->kv_elem; a.max_seq = e->maxseq;
-    a.st = e->d_st; a.tokens_out = e->w_tokens; a.logits = e->d_logits;
+    a.st = p.st; a.tokens_out = p.w_tokens; a.logits = p.logits;
     a.gran = e->d_gran; a.serial = e->d_serial; a.err = e->d_err; a.trace = trace;
-    launched(launch_persist_decode(a, s), "persistent decode");
+    launched(launch_persist_decode(a, p.s), "persistent decode");
 }
 
 // the persistent step reports a bounded wait that expired through a device word: turn it into an error (and clear it)
@@ -82,14 +85,9 @@ void check_persist_error(ma_engine* e, hipStream_t s) {
     }
 }
 
-// ---- the parts of init_state / build_engine that exist for these forms only (called where the blocks stood, so the order of device allocations stays)
-void exp_reset_exchanges(ma_engine* e, hipStream_t s) {
-    HIP_CHECK(hipMemsetAsync(e->d_part_gran, 0, (size_t)e->cfg.max_batch * e->cfg.heads * ATTN_NCHUNK * RF_PART * sizeof(u64), s));
-}
+// ---- the parts of build_engine that exist for these forms only (called where the blocks stood, so the order of device allocations stays)
 void exp_alloc_exchanges(ma_engine* e) {
-    const size_t n = (size_t)e->cfg.max_batch * (size_t)e->cfg.heads * ATTN_NCHUNK * RF_PART;
-    e->d_part_gran = e->dmalloc<u64>(n);
-    HIP_CHECK(hipMemset(e->d_part_gran, 0, n * sizeof(u64)));
+    e->d_part_gran = e->xalloc<u64>((size_t)e->cfg.max_batch * (size_t)e->cfg.heads * ATTN_NCHUNK * RF_PART);
 }
 int exp_layer_pair_occupancy() {
     int occ = 0;
@@ -109,12 +107,10 @@ void exp_build_gates(ma_engine* e, const hipDeviceProp_t& prop) {
     if (e->persist_shape && persist_prepare() != hipSuccess) { (void)hipGetLastError(); e->persist_shape = false; }
     if (!e->persist_shape) return;
     e->d_layers = e->dmalloc<DecLayerPtrs>(c.layers);
-    e->d_gran = e->dmalloc<u64>(PG_TOTAL); e->d_serial = e->dmalloc<unsigned>(1); e->d_err = e->dmalloc<unsigned>(1);
+    e->d_gran = e->xalloc<u64>(PG_TOTAL, 0); e->d_serial = e->dmalloc<unsigned>(1); e->d_err = e->xalloc<unsigned>(1, 0);      // (zeroed once: the persistent step's exchanges are not reset per generation)
     e->d_ptrace = e->dmalloc<u64>((size_t)PS_CUS * (PS_TRACE_EVENTS + PS_TRACE2_EVENTS));
-    HIP_CHECK(hipMemset(e->d_gran, 0, PG_TOTAL * sizeof(u64)));
     const unsigned one = 1u;
     HIP_CHECK(hipMemcpy(e->d_serial, &one, sizeof(unsigned), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(e->d_err, 0, sizeof(unsigned)));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_err), sizeof(unsigned)));
 }
 void exp_upload_layers(ma_engine* e) {
@@ -129,10 +125,11 @@ void persist_trace(ma_engine* e, int kv_len, uint64_t* host_out, int32_t* n_even
     ensure_embtab(e, s);
     state_at(e, s, 1, kv_len);
     StepTimer none;
-    for (int i = 0; i < 3; ++i) enqueue_persist_step(e, s, none);
+    Step p(e, s, none, Rows{0, 1});
+    for (int i = 0; i < 3; ++i) enqueue_persist_step(p);
     const size_t tr_words = (size_t)PS_CUS * (PS_TRACE_EVENTS + PS_TRACE2_EVENTS);
     HIP_CHECK(hipMemsetAsync(e->d_ptrace, 0, tr_words * sizeof(u64), s));
-    enqueue_persist_step(e, s, none, e->d_ptrace);
+    enqueue_persist_step(p, e->d_ptrace);
     HIP_CHECK(hipMemcpyAsync(host_out, e->d_ptrace, tr_words * sizeof(u64), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     check_persist_error(e, s);
