@@ -25,6 +25,9 @@ struct AttnArgs {
     int round_bf16;
     // batch of independent samples: grid.z = sample, element strides between samples (0 / 1 launch at batch 1)
     size_t q_bs = 0, k_bs = 0, v_bs = 0, o_bs = 0; int batch = 1;
+    // > 0 (attn2.hpp only; < 0: none): the LAST sample of the batch has Sq = Sk = last_len rows -- what its tensors hold behind them is neither read nor written
+    // (the two-stream prefill, engine_dense.hpp: those rows belong to the other stream)
+    int last_len = -1;
 };
 
 typedef float attn_f32x16 __attribute__((ext_vector_type(16)));
@@ -312,6 +315,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs a) {
 // engine's bf16 policy) | == 0 (fp32 "exact" policy) and 2: the exact-fp32 VALU kernel above
 inline hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     if (a.Sq <= 0) return hipSuccess;
+    if (a.last_len >= 0) return hipErrorInvalidValue;       // (attn2.hpp only)
     if (a.round_bf16 == 1) hipLaunchKernelGGL(attention_mfma_kernel<float>, dim3((a.Sq + 63) / 64, a.H, a.batch), dim3(256), 0, s, a);
     else if (a.round_bf16 == 3) hipLaunchKernelGGL(attention_mfma_kernel<bf16_t>, dim3((a.Sq + 63) / 64, a.H, a.batch), dim3(256), 0, s, a);
     else {

@@ -47,6 +47,7 @@ struct Attn2Args {
     float scale;
     int causal_offset;                  // < 0: full attention; else query i sees keys <= causal_offset + i
     size_t q_bs, k_bs, o_bs;            // element strides between the samples of a batch (grid.z)
+    int Sq_last, Sk_last;               // ... of the LAST sample of the batch (AttnArgs::last_len; = Sq, Sk when it has them all)
 };
 
 __device__ __forceinline__ int a2_slot(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
@@ -60,9 +61,11 @@ template <typename HT> __device__ __forceinline__ uint32_t a2_pack(float lo, flo
 
 // V (Sk rows x 64 d per head, row stride v_rs, head offset h * v_hs) -> V^T [batch][H][64][skp], zero beyond Sk, the keys of every
 // aligned 16 stored in the order {0-3, 8-11, 4-7, 12-15}.  One block = one 64-key tile of one (sample, head).
-__global__ __launch_bounds__(256) void vt_pack_kernel(const bf16_t* __restrict__ V, int v_rs, int v_hs, size_t v_bs, bf16_t* __restrict__ VT, int Sk, int skp, int H) {
+// The last sample of the batch has Sk_last keys (<= Sk): nothing behind them is read, the tile is zero there as well.
+__global__ __launch_bounds__(256) void vt_pack_kernel(const bf16_t* __restrict__ V, int v_rs, int v_hs, size_t v_bs, bf16_t* __restrict__ VT, int Sk, int skp, int H, int Sk_last) {
     __shared__ bf16_t t[64][66];        // [key][d], padded: the column reads below walk the keys
     const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, k0 = blockIdx.x * 64;
+    if (b == (int)gridDim.z - 1) Sk = Sk_last;
     const bf16_t* vp = V + (size_t)b * v_bs + (size_t)h * v_hs;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -101,11 +104,14 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_mfma2_kernel(Attn2Args a
     __shared__ __attribute__((aligned(16))) char smem[NST * 2 * TILE]; // ring of three stages x {K, V^T}; reused for the output patches
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), ln = lane & 31, hi = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z, q0 = blockIdx.x * RB;
+    // (the last sample of a batch may be shorter, AttnArgs::last_len: what lies behind its rows is neither read nor written)
+    const bool short_one = b == (int)gridDim.z - 1;
+    const int Sq = short_one ? a.Sq_last : a.Sq, Sk = short_one ? a.Sk_last : a.Sk;
     const bf16_t* Qp = a.Q + (size_t)b * a.q_bs + (size_t)h * a.q_hs;
     const bf16_t* Kp = a.K + (size_t)b * a.k_bs + (size_t)h * a.k_hs;
     const bf16_t* Vp = a.VT + ((size_t)b * a.H + h) * 64 * a.skp;
     const int qrow = q0 + w * 32 + ln;                                  // this lane's query
-    const bool qok = qrow < a.Sq;
+    const bool qok = qrow < Sq;
 
     // Q^T fragments: B[k = d][n = query]: lane (query ln, k group hi) holds d = 16 s + 8 hi .. + 7 for the four 16-deep steps
     u32x4 qf[4];
@@ -116,8 +122,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_mfma2_kernel(Attn2Args a
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const u32x4*>(qp + 16 * s);
     }
-    int kv_end = a.Sk;
-    if (a.causal_offset >= 0) kv_end = min(a.Sk, a.causal_offset + min(q0 + RB - 1, a.Sq - 1) + 1);
+    int kv_end = Sk;
+    if (a.causal_offset >= 0) kv_end = min(Sk, a.causal_offset + min(q0 + RB - 1, Sq - 1) + 1);
     const int nt = (kv_end + 63) >> 6;
 
     // LDS-DMA of tile t into ring stage t % 3: 16 pieces of 1 KiB (8 K pieces = 8 key rows each, 8 V^T pieces = 8 d rows each), piece p by wave p % NW.
@@ -134,7 +140,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_mfma2_kernel(Attn2Args a
             const int p = w + NW * i;                                    // (wave-uniform)
             if (NW * i + NW > 16 && p >= 16) continue;
             const int r = (p & 7) * 8 + drow, c = dslot ^ ((r >> 1) & 7);
-            const bf16_t* ks = Kp + (size_t)min(kv0 + r, a.Sk - 1) * a.k_rs + c * 8;
+            const bf16_t* ks = Kp + (size_t)min(kv0 + r, Sk - 1) * a.k_rs + c * 8;
             const bf16_t* vs = Vp + (size_t)r * a.skp + kv0 + c * 8;
             gt_glds16(p < 8 ? ks : vs, __builtin_amdgcn_readfirstlane(base + (unsigned)p * 1024u));
         }
@@ -178,8 +184,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_mfma2_kernel(Attn2Args a
         //  (scores stay raw, the running maximum is kept in the scaled domain: one multiply per tile instead of 32); the output accumulators are rescaled
         //  only when some row's maximum moved.)
         const int kbase = (t << 6) + 4 * hi;
-        const int klimit = a.causal_offset >= 0 ? min(a.Sk - 1, a.causal_offset + qrow) : a.Sk - 1;       // last visible key of this lane's query
-        const int klimit_wave = a.causal_offset >= 0 ? min(a.Sk - 1, a.causal_offset + q0 + w * 32) : a.Sk - 1;      // ... of the wave's first row: the smallest
+        const int klimit = a.causal_offset >= 0 ? min(Sk - 1, a.causal_offset + qrow) : Sk - 1;       // last visible key of this lane's query
+        const int klimit_wave = a.causal_offset >= 0 ? min(Sk - 1, a.causal_offset + q0 + w * 32) : Sk - 1;      // ... of the wave's first row: the smallest
         float mx = -INFINITY;
         if ((t << 6) + 63 <= klimit_wave) {
 #pragma unroll
@@ -258,7 +264,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_mfma2_kernel(Attn2Args a
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int id = lane + 64 * i, r = id >> 3, c = id & 7, row = q0 + w * 32 + r;
-        if (row < a.Sq) *reinterpret_cast<u32x4*>(Op + (size_t)row * a.o_rs + c * 8) = *reinterpret_cast<const u32x4*>(patch + r * 128 + a2_slot(r, c) * 16);
+        if (row < Sq) *reinterpret_cast<u32x4*>(Op + (size_t)row * a.o_rs + c * 8) = *reinterpret_cast<const u32x4*>(patch + r * 128 + a2_slot(r, c) * 16);
     }
 }
 
@@ -269,10 +275,12 @@ template <typename HT>
 inline hipError_t launch_attention2(const AttnArgs& a, bf16_t* vt, hipStream_t s) {
     if (a.Sq <= 0 || a.Sk <= 0) return hipSuccess;
     const int skp = (a.Sk + 63) & ~63;
+    if (a.last_len == 0 || a.last_len > a.Sq || a.last_len > a.Sk) return hipErrorInvalidValue;
+    const int Sq_last = a.last_len > 0 ? a.last_len : a.Sq, Sk_last = a.last_len > 0 ? a.last_len : a.Sk;
     if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs) % 8) return hipErrorInvalidValue;      // 16-byte vector accesses
-    hipLaunchKernelGGL(vt_pack_kernel, dim3(skp / 64, a.H, a.batch), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(a.V), a.v_rs, a.v_hs, a.v_bs, vt, a.Sk, skp, a.H);
+    hipLaunchKernelGGL(vt_pack_kernel, dim3(skp / 64, a.H, a.batch), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(a.V), a.v_rs, a.v_hs, a.v_bs, vt, a.Sk, skp, a.H, Sk_last);
     Attn2Args g{reinterpret_cast<const bf16_t*>(a.Q), a.q_rs, a.q_hs, reinterpret_cast<const bf16_t*>(a.K), a.k_rs, a.k_hs, vt, reinterpret_cast<bf16_t*>(a.O), a.o_rs,
-                a.Sq, a.Sk, skp, a.H, a.scale, a.causal_offset, a.q_bs, a.k_bs, a.o_bs};
+                a.Sq, a.Sk, skp, a.H, a.scale, a.causal_offset, a.q_bs, a.k_bs, a.o_bs, Sq_last, Sk_last};
     // 96-row blocks when they waste fewer rows than 128-row blocks (257 rows: 288 vs 384)
     const int pad3 = (a.Sq + 95) / 96 * 96, pad4 = (a.Sq + 127) / 128 * 128;
     if (pad3 < pad4) hipLaunchKernelGGL((attention_mfma2_kernel<3, HT>), dim3(pad3 / 96, a.H, a.batch), dim3(192), 0, s, g);

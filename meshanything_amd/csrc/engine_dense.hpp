@@ -25,7 +25,7 @@ struct ResLnBufs { float* h; void* hb; float* y; };       // gemm_res_ln: the fp
 // attention operands: element strides between rows (rs), heads (hs) and samples (bs); the output's heads are 64 apart
 struct AttnView { const void* p; int rs, hs; size_t bs = 0; };
 struct AttnOut { void* p; int rs; size_t bs = 0; };
-struct AttnShape { int Sq, Sk, heads, causal_offset, batch = 1; };
+struct AttnShape { int Sq, Sk, heads, causal_offset, batch = 1, last_len = -1; };      // (last_len: AttnArgs, attn.hpp)
 struct AttnOpts { bf16_t* vt = nullptr; size_t vt_elems = 0; };      // a V^T workspace other than the engine's (attn2.hpp)
 // out = (mask ? in : 0) + t0 + tab[(i % tab_mod) + row0] -> fp32 (out32, may alias in) and activation copy (outa, optional): add_rows2_kernel
 struct AddRows {
@@ -110,7 +110,7 @@ struct Dense {
     // attention over activation tensors; sh.batch = samples (grid.z)
     void attention(AttnView q, AttnView k, AttnView v, AttnOut o, AttnShape sh, const AttnOpts& w = {}) const {
         AttnArgs a{q.p, q.rs, q.hs, k.p, k.rs, k.hs, v.p, v.rs, v.hs, o.p, o.rs, sh.Sq, sh.Sk, sh.heads, 0.125f, sh.causal_offset, is16 ? 3 : 0};
-        a.batch = sh.batch; a.q_bs = q.bs; a.k_bs = k.bs; a.v_bs = v.bs; a.o_bs = o.bs;
+        a.batch = sh.batch; a.last_len = sh.last_len; a.q_bs = q.bs; a.k_bs = k.bs; a.v_bs = v.bs; a.o_bs = o.bs;
         if (is16 && (e->opt.attn_impl == 2 || e->hdt == MA_DTYPE_F16)) {     // (the first-generation kernel, attn_impl 1, is bf16 only)
             if (attn2_vt_elems(sh.Sk, sh.heads, sh.batch) > (w.vt ? w.vt_elems : e->vt_elems)) throw MaError(MA_ERR_INVALID, "internal: V^T workspace too small");
             HIP_CHECK(H16_CALL(e->hdt, HT, launch_attention2<HT>(a, w.vt ? w.vt : e->a_vt, s)));
@@ -236,11 +236,14 @@ void prefill(const Dense& d, const float* prefix, int row0, int B) {
     // prefill).  Those rows are the LAST B positions of the LAST sample: causal attention means no other row ever reads anything of theirs, so the rows in
     // front of them (`part 1`: exact tile rows, no tail launches) run all 24 layers without them, and they (`part 2`) follow on a second stream with the same
     // kernels the one-stream form gives them -- each of their layers needs from the main chain only that layer's K / V of the earlier positions (one event
-    // per layer).  The main chain's attention still launches over all B x T query rows: the last B of them are stale rows of the q|k|v buffer, their output
-    // goes to rows of `att` nobody reads (the tail chain has its own), and what they do to keys they can see but that the tail chain is still writing is
-    // masked in every valid row (the planes are zeroed at creation, so a masked V is a finite number).  Same bits as the one-stream form.
+    // per layer).  Neither chain touches what the other owns: the main chain's attention (and the V^T packing in front of it) takes the last sample as
+    // T - nt rows and T - nt keys (AttnShape::last_len -- those rows never see a later key), so positions T - nt .. T - 1 of that sample's planes,
+    // which the tail chain writes at a time of its own choosing, are read by the tail chain alone, behind its own writes, and the stale last rows of the
+    // q|k|v buffer by nobody.  What a plane holds there from an earlier generation (it need not be finite: a masked probability is 0, and 0 x inf is
+    // not) never reaches a kernel.  Same bits as the one-stream form: the keys left out were masked in every row that is kept.
     const int Mm = M - M % 256;
-    const bool tail = e->opt.prefill_tail && d.is16 && B >= 8 && M > Mm && M - Mm <= 64 && M - Mm <= T && e->a_patt_tail && attn2_vt_elems(T, c.heads, 1) <= e->vt_tail_elems;
+    const bool attn2 = e->opt.attn_impl == 2 || e->hdt == MA_DTYPE_F16;      // (the kernel that knows AttnShape::last_len)
+    const bool tail = e->opt.prefill_tail && d.is16 && attn2 && B >= 8 && M > Mm && M - Mm <= 64 && M - Mm <= T && e->a_patt_tail && attn2_vt_elems(T, c.heads, 1) <= e->vt_tail_elems;
     hipStream_t s2 = nullptr;
     if (tail) {
         if (!e->tail_stream) {
@@ -268,7 +271,7 @@ void prefill(const Dense& d, const float* prefix, int row0, int B) {
     for (int l = 0; l < c.layers; ++l) {
         const PostLnLayerW& w = e->dw.opt[l];
         const size_t q_bs = (size_t)T * 3 * H;
-        const AttnShape causal{.Sq = T, .Sk = T, .heads = c.heads, .causal_offset = 0, .batch = B};
+        const AttnShape causal{.Sq = T, .Sk = T, .heads = c.heads, .causal_offset = 0, .batch = B, .last_len = tail ? T - (M - Mm) : -1};
         if (d.is16) {
             // 16-bit policies: the K / V columns of the rows on the persistent 256 x 256 tiles go straight into the cache planes (gemm256.hpp, KV form);
             // the rows behind them (the 64-row tail of M = B x 257; every row when another kernel took the GEMM) are copied from the q|k|v tensor.

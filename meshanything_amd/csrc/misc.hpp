@@ -265,7 +265,8 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
     if (tid == 0) {
         if (t < sv.max_new) tokens_out[t] = picked;
         if (tok == TOK_EOS) st->finished = 1;
-        st->cur_tok = tok;
+        st->cur_tok = tk;         // (the CLAMPED token: without embed_table the next step's embedding launch indexes the codebook with it -- an all-NaN row's
+                                  //  "no argmax" index, 0x7fffffff, sent that read far outside the table)
         st->t = t + 1;
         st->pos = T + t;          // next step feeds token t at cache row cond_length + (t+1) - 1
     }

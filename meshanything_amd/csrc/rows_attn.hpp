@@ -149,12 +149,15 @@ __global__ __launch_bounds__(512) void rows_attn_kernel(RowsAttnArgs a) {
     // Slots past the end: their scores are masked, but their REQUESTS are real.  The first version clamped them to the plane and so streamed
     // two or three useless rounds per block at short caches (step at kv 600: 717 us; 668 us since).  A slot past the end now asks for the position
     // of slot 0 of ITS OWN wave-load (the eight positions of a wave-load are one request each: the lanes of a dead slot fold into a live one), for
-    // the newest position if that is dead too (one request for the whole instruction), and a round entirely past the end is not requested at all.
+    // position 0 if that is dead too or the newest one (one request for the whole instruction), and a round entirely past the end is not requested at all.
     // PMC, 256 generated steps at 8 rows (cache 257 .. 513): 23.0 MB per launch against 21.0 MB algorithmic (8.4 MB of q/k/v + out_proj weights
     // + 8 rows x 385 positions x 4 KB) = 1.10x, profiles/r05_pmc_decode_traffic_b8.json.
     auto kv_pos = [&](int base, int u) -> size_t {
         const int p = base + u * PPW, p0 = p - slot;          // this slot's position; slot 0's of the same wave-load
-        return (size_t)(p < end ? p : p0 < end ? p0 : pos);
+        // (never the newest position itself: its row of the plane is written by THIS launch, at a time of its own -- until then it holds what an earlier
+        //  generation left there, which need not be finite, and a dead slot's value is multiplied by a probability of 0, not selected away: 0 x NaN.
+        //  Position 0 is always there, and written by the prefill.)
+        return (size_t)(p < end ? p : p0 < pos ? p0 : 0);
     };
     auto early = [&](int rr, u32x4 (&kr)[U], u32x4 (&vr)[U]) {
         if ((g0 + 2 * rr) * RPOS >= end) return;              // (block-uniform: the whole round is past the end; its registers are never reduced)
