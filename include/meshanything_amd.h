@@ -385,6 +385,31 @@ MA_API int  ma_op_sample_surface(const double *verts, int nv, const int32_t *fac
  *   ma_op_sample_surface applies, exposed so that it can be checked without a device. */
 MA_API int  ma_f64_to_f16(const double *x, int64_t n, uint16_t *out);
 
+/* ---- best-of-N sampling: scores of candidate meshes against the cloud they were generated from (csrc/mesh_score.hpp).  Has no reference
+ * counterpart (the reference draws one mesh per cloud; a bad draw is re-run by hand with another seed).  Needs no engine; errors via
+ * ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`.
+ *
+ * ma_op_score_meshes: coords (B, F, 3, 3) fp32 = the detokenizer's output as it is: a face with any non-finite coordinate is invalid and
+ *   skipped (the NaN rows of meshanything.py:69-78); every vertex is multiplied by mesh_scale before use.  cloud (B / n_per_cloud, P,
+ *   cloud_ld) fp32 with xyz in the first three columns of a row, cloud_ld = 3 or 6 (a pc_normal tensor); candidate b is scored against
+ *   cloud b / n_per_cloud.  scores (B, 4) fp32:
+ *     [0] cloud to mesh: the mean over the P points of the distance to the nearest valid face; a face whose inradius is below 2^-20 (fp32
+ *         cannot resolve its plane) counts as its three edges, as in ma_op_mesh_udf
+ *     [1] mesh to cloud: sum_f area_f * (1/7) sum_k nn(q_fk) / sum_f area_f over the valid faces, q_fk = the 3 vertices, the 3 edge
+ *         midpoints and the centroid of face f, nn = the distance to the nearest cloud point
+ *     [2] sum_f area_f of the scaled mesh      [3] the number of valid faces
+ *   [0] = [1] = +inf for a candidate without a valid face, [1] = +inf when every valid face has zero area; no output is NaN.
+ *   Bitwise reproducible, and a candidate's four numbers do not depend on B or on NaN rows between its valid faces: per-point and
+ *   per-face terms go to the workspace in fp32 (pt_dist (B, P) | face_nn (B, F) | face_area (B, F), -1 = invalid; each part aligned to
+ *   256 bytes) and are summed in fp64 in a fixed order; no float atomics.
+ *   B >= 1, B % n_per_cloud == 0, 1 <= F <= MA_SCORE_MESHES_MAX_FACES, 1 <= P <= MA_SCORE_MESHES_MAX_POINTS, mesh_scale finite and > 0.
+ *   workspace: ma_score_meshes_workspace_bytes(B, F, P) bytes of device memory (0 for arguments outside those limits). */
+#define MA_SCORE_MESHES_MAX_FACES (1 << 20)
+#define MA_SCORE_MESHES_MAX_POINTS (1 << 20)
+MA_API int    ma_op_score_meshes(const float *coords, int B, int F, const float *cloud, int cloud_ld, int P, int n_per_cloud, float mesh_scale,
+                                 float *scores, void *workspace, size_t ws_bytes, void *stream);
+MA_API size_t ma_score_meshes_workspace_bytes(int B, int F, int P);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ read from `--pretrained_weights` (the reference ignores that flag and downloads 
 .stl and samples the surface in numpy (`meshanything_amd/mesh_input.py`; with the extra flag `--gpu_sampling` the same samples come from
 HIP kernels, `meshanything_amd/surface_sample.py`), `--mc` makes the input watertight on the GPU first
 (`meshanything_amd/watertight.py`: unsigned distance + marching cubes in HIP instead of mesh2sdf + scikit-image); the
-mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.
+mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.  One flag the reference does
+not have: `--sampling --num_candidates N` draws N meshes per input in one batch and writes the one closest to the input cloud
+(`meshanything_amd/mesh_score.py`).
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -25,7 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def get_args():
+def get_args(argv=None):
     p = argparse.ArgumentParser("MeshAnything", add_help=True)
     p.add_argument("--llm", default="facebook/opt-350m", type=str)
     p.add_argument("--input_dir", default=None, type=str)
@@ -44,7 +46,14 @@ def get_args():
     p.add_argument("--gpu_sampling", default=False, action="store_true",
                    help="sample mesh inputs (and the --mc surface) on the GPU: the same draws and clouds as the host sampler")
     p.add_argument("--synthetic_weights", default=False, action="store_true", help="seeded random checkpoint (no released file offline)")
-    return p.parse_args()
+    p.add_argument("--num_candidates", default=1, type=int,
+                   help="with --sampling: draw this many meshes per input in one batch and keep the one closest to the input cloud")
+    args = p.parse_args(argv)
+    if args.num_candidates < 1:
+        p.error("--num_candidates must be >= 1")
+    if args.num_candidates > 1 and not args.sampling:
+        p.error("--num_candidates > 1 needs --sampling (greedy candidates are identical)")
+    return args
 
 
 def main():
@@ -98,7 +107,13 @@ def main():
     for batch in dp.batches(mine, args.batchsize_per_gpu):
         data = [dataset[i] for i in batch]
         pc = torch.from_numpy(np.stack([d["pc_normal"] for d in data])).cuda()
-        outputs = model(pc, sampling=args.sampling).cpu().numpy()
+        if args.num_candidates > 1:
+            det = model.forward_detailed(pc, sampling=True, num_candidates=args.num_candidates)
+            outputs = det["coords"].cpu().numpy()
+            for d, c, tot in zip(data, det["chosen"].tolist(), det["total"].tolist()):
+                print(f'{d["uid"]}: candidate {c} of {args.num_candidates} chosen, totals ' + " ".join(f"{t:.6f}" for t in tot))
+        else:
+            outputs = model(pc, sampling=args.sampling).cpu().numpy()
         for d, coords in zip(data, outputs):
             verts, faces = faces_from_coords(coords)
             faces = fix_normals(verts, faces)

@@ -39,6 +39,7 @@
 #include "state.hpp"
 #include "surface_sample.hpp"
 #include "watertight.hpp"
+#include "mesh_score.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -887,6 +888,24 @@ int ma_f64_to_f16(const double* x, int64_t n, uint16_t* out) {
     if (!x || !out || n < 0) return MA_ERR_INVALID;
     for (int64_t i = 0; i < n; ++i) out[i] = ss::f64_to_f16_rne(x[i]);
     return MA_OK;
+}
+
+// ---- best-of-N candidate scores (csrc/mesh_score.hpp) -------------------------------------------------------------------------
+static bool score_shape_ok(int B, int F, int P) { return B >= 1 && F >= 1 && F <= MA_SCORE_MESHES_MAX_FACES && P >= 1 && P <= MA_SCORE_MESHES_MAX_POINTS; }
+
+size_t ma_score_meshes_workspace_bytes(int B, int F, int P) { return score_shape_ok(B, F, P) ? score::score_ws_bytes(B, F, P) : 0; }
+
+int ma_op_score_meshes(const float* coords, int B, int F, const float* cloud, int cloud_ld, int P, int n_per_cloud, float mesh_scale, float* scores,
+                       void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!coords || !cloud || !scores || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: null pointer");
+        if (!score_shape_ok(B, F, P)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: need B >= 1, 1 <= F <= 2^20 and 1 <= P <= 2^20");
+        if (n_per_cloud < 1 || B % n_per_cloud) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: n_per_cloud must be >= 1 and divide B");
+        if (cloud_ld != 3 && cloud_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: cloud_ld must be 3 or 6");
+        if (!std::isfinite(mesh_scale) || !(mesh_scale > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: mesh_scale must be finite and > 0");
+        if (ws_bytes < score::score_ws_bytes(B, F, P)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: workspace smaller than ma_score_meshes_workspace_bytes(B, F, P)");
+        HIP_CHECK(score::launch_score_meshes(coords, B, F, cloud, cloud_ld, P, n_per_cloud, mesh_scale, scores, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
 }
 
 }  // extern "C"

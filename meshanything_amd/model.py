@@ -17,7 +17,10 @@ thin call into libmeshanything_amd.so through `Engine` (no arithmetic happens in
 
 `args` needs the attributes the reference reads: `.llm` (config name only; ignored like the reference ignores its
 weights), `.codebook_size`, `.codebook_dim`, `.n_max_triangles` (meshanything.py:19-20,93,96).  Extra, optional:
-`.dtype` ("bf16" | "fp16" | "fp32"), `.batchsize_per_gpu` (engine max_batch), `.device` (GPU index).
+`.dtype` ("bf16" | "fp16" | "fp32"), `.batchsize_per_gpu` and `.num_candidates` (engine max_batch = their product), `.device` (GPU index).
+
+Not in the reference: `model(pc_normal, sampling=True, num_candidates=N)` draws N meshes per cloud in one batch and returns the one
+closest to its cloud (mesh_score.py).
 """
 from __future__ import annotations
 
@@ -37,8 +40,8 @@ def config_from_args(args) -> MAConfig:
         return args.ma_config
     dtype = {"bf16": DTYPE_BF16, "fp16": DTYPE_F16, "fp32": DTYPE_F32}[getattr(args, "dtype", "bf16")]
     return MAConfig.full(codebook_size=int(getattr(args, "codebook_size", 8192)), codebook_dim=int(getattr(args, "codebook_dim", 1024)),
-                         n_max_faces=int(getattr(args, "n_max_triangles", 800)), max_batch=int(getattr(args, "batchsize_per_gpu", 1)),
-                         dtype=dtype)
+                         n_max_faces=int(getattr(args, "n_max_triangles", 800)),
+                         max_batch=int(getattr(args, "batchsize_per_gpu", 1)) * max(1, int(getattr(args, "num_candidates", 1))), dtype=dtype)
 
 
 class PointEncoder:
@@ -161,13 +164,47 @@ class MeshAnything(torch.nn.Module):
         return z ^ (z >> 31)
 
     @torch.no_grad()
-    def forward(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None) -> torch.Tensor:
+    def forward(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, num_candidates: int = 1) -> torch.Tensor:
         """(B, 4096, 6) -> (B, n_max_triangles, 3, 3) fp32, NaN rows = invalid faces (meshanything.py:134-176): one library call.
-        `seed` (optional) pins the sampler's uniform stream for this call; by default it advances from call to call."""
-        return self.forward_detailed(pc_normal, sampling, seed=seed)["coords"]
+        `seed` (optional) pins the sampler's uniform stream for this call; by default it advances from call to call.
+        `num_candidates` N > 1 (needs sampling): N meshes per cloud, the one closest to its cloud is returned (forward_detailed)."""
+        return self.forward_detailed(pc_normal, sampling, seed=seed, num_candidates=num_candidates)["coords"]
 
     @torch.no_grad()
-    def forward_detailed(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, **kw) -> Dict[str, object]:
-        """forward() plus the intermediate tensors (tokens, lengths, ids, latents) for tests and tooling."""
+    def forward_detailed(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, num_candidates: int = 1,
+                         **kw) -> Dict[str, object]:
+        """forward() plus the intermediate tensors (tokens, lengths, ids, latents) for tests and tooling.  With num_candidates N > 1:
+        coords (G, F, 3, 3) = the chosen candidate of each cloud, candidates (G, N, F, 3, 3), scores (G, N, 4) (mesh_score.score_meshes;
+        `mesh_scale` may be passed), total (G, N), chosen (G,), and tokens, lengths, ids, latents of all G * N rows (row g * N + i)."""
+        n = int(num_candidates)
+        if n < 1:
+            raise ValueError(f"num_candidates must be >= 1, got {num_candidates}")
+        if n > 1:
+            return self._best_of_n(pc_normal, bool(sampling), seed, n, **kw)
         s = self._next_stream_seed() if seed is None else int(seed)
         return self.engine.forward(pc_normal, sampling=bool(sampling), seed=s, **kw)
+
+    def _best_of_n(self, pc_normal: torch.Tensor, sampling: bool, seed: Optional[int], n: int, mesh_scale: Optional[float] = None,
+                   **kw) -> Dict[str, object]:
+        """Encode the G clouds once, decode G * n rows in one generate() -- the sampler's uniform stream is keyed by (seed, row, step), so
+        the rows of a group differ --, detokenize, score every row against its cloud on the GPU and keep the best of each group."""
+        from .mesh_score import DEFAULT_MESH_SCALE, score_meshes, select
+        if not sampling:
+            raise ValueError("num_candidates > 1 needs sampling=True: greedy candidates are identical")
+        G = pc_normal.shape[0]
+        if G * n > self.cfg.max_batch:
+            raise ValueError(f"{G} clouds x num_candidates {n} = {G * n} rows exceed the engine's max_batch {self.cfg.max_batch} "
+                             f"(= batchsize_per_gpu * num_candidates the model was built with)")
+        s = self._next_stream_seed() if seed is None else int(seed)
+        eng = self.engine
+        latents, prefix = eng.encode(pc_normal)
+        latents = latents.repeat_interleave(n, dim=0)
+        tokens, lengths = eng.generate(prefix.repeat_interleave(n, dim=0), sampling=True, seed=s, **kw)
+        ids = eng.postprocess_tokens(tokens)
+        cand = eng.detokenize(ids, latents)
+        scores = score_meshes(cand, pc_normal.to(cand.device), n, DEFAULT_MESH_SCALE if mesh_scale is None else mesh_scale)
+        chosen, total = select(scores, n)
+        cand = cand.view(G, n, *cand.shape[1:])
+        coords = cand[torch.arange(G, device=cand.device), chosen]
+        return {"coords": coords, "candidates": cand, "scores": scores.view(G, n, 4), "total": total, "chosen": chosen, "tokens": tokens,
+                "lengths": lengths, "ids": ids, "latents": latents}
