@@ -410,6 +410,38 @@ MA_API int    ma_op_score_meshes(const float *coords, int B, int F, const float 
                                  float *scores, void *workspace, size_t ws_bytes, void *stream);
 MA_API size_t ma_score_meshes_workspace_bytes(int B, int F, int P);
 
+/* ---- normals of a raw point cloud, for --input_type pc_xyz (csrc/pc_normals.hpp).  Has no reference counterpart: the reference takes only
+ * clouds that already carry unit normals (pc_normal), or meshes.  Needs no engine; errors via ma_last_error(NULL); every argument is
+ * checked before the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`.  No atomics: bitwise reproducible.
+ *
+ * ma_op_pc_knn: for the Q rows query_idx[q] (int32) of ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6 -- or for
+ *   every row when query_idx is NULL (then Q must equal N) -- the k nearest rows of ref: nbr_idx (Q, k) int32 and nbr_d2 (Q, k) fp32,
+ *   nearest first.  The key of row r for a query at (qx, qy, qz) is exactly
+ *       d = fl32(fl32(dx * dx + dy * dy) + dz * dz),  dx = fl32(qx - rx), dy = fl32(qy - ry), dz = fl32(qz - rz)
+ *   (no FMA contraction; a NaN key, which only non-finite coordinates produce, counts as +inf) and neighbours are ordered by the pair
+ *   (d, r) ascending.  That is a total order: a point is its own neighbour at distance 0, duplicates are ordinary points, and a numpy
+ *   float32 restatement gives the same bits.  The reference range is searched in `splits` chunks by separate workgroups whose partial
+ *   lists a second kernel merges; the result does not depend on splits, bit for bit.  splits = 0: the implementation's choice, a
+ *   function of N and Q alone.  An index of query_idx outside [0, N) is clamped into it.
+ *   MA_PC_KNN_MIN_K <= k <= MA_PC_KNN_MAX_K, k <= N <= MA_PC_KNN_MAX_POINTS, 1 <= Q <= MA_PC_KNN_MAX_QUERIES, 0 <= splits <=
+ *   MA_PC_KNN_MAX_SPLITS.  workspace: ma_pc_knn_workspace_bytes(N, Q, k, splits) bytes of device memory (0 for arguments outside those
+ *   limits).
+ * ma_op_pc_normals: per query q, from the k rows nbr_idx[q] of ref, in float64 without FMA contraction: the centroid c = (sum x) / k, the
+ *   covariance (sum (x - c)(x - c)^T) / k, both summed in list order; eigvals (Q, 3) float64 ascending and normals (Q, 3) float64 = the
+ *   unit eigenvector of the smallest (cyclic Jacobi), signed so that its component of largest magnitude is positive, the lowest axis
+ *   on ties.  Always unit and finite: k coincident neighbours give (0, 0, 1) and zero eigenvalues; a collinear neighbourhood gives
+ *   some unit perpendicular, unspecified but deterministic.  An index outside [0, N) is clamped into it.  Same limits on N, Q, k. */
+#define MA_PC_KNN_MIN_K 3
+#define MA_PC_KNN_MAX_K 32
+#define MA_PC_KNN_MAX_POINTS (1 << 22)
+#define MA_PC_KNN_MAX_QUERIES (1 << 20)
+#define MA_PC_KNN_MAX_SPLITS 64
+MA_API int    ma_op_pc_knn(const float *ref, int N, int ref_ld, const int32_t *query_idx, int Q, int k, int splits, int32_t *nbr_idx,
+                           float *nbr_d2, void *workspace, size_t ws_bytes, void *stream);
+MA_API size_t ma_pc_knn_workspace_bytes(int N, int Q, int k, int splits);
+MA_API int    ma_op_pc_normals(const float *ref, int N, int ref_ld, const int32_t *nbr_idx, int Q, int k, double *normals, double *eigvals,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

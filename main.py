@@ -12,7 +12,8 @@ HIP kernels, `meshanything_amd/surface_sample.py`), `--mc` makes the input water
 (`meshanything_amd/watertight.py`: unsigned distance + marching cubes in HIP instead of mesh2sdf + scikit-image); the
 mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.  One flag the reference does
 not have: `--sampling --num_candidates N` draws N meshes per input in one batch and writes the one closest to the input cloud
-(`meshanything_amd/mesh_score.py`).
+(`meshanything_amd/mesh_score.py`).  And one input type it does not have: `--input_type pc_xyz` takes points WITHOUT normals (.npy of
+shape (N, >= 3), .xyz or .txt) and estimates them on the GPU from `--normal_k` neighbours (`meshanything_amd/pc_normals.py`).
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -34,7 +35,7 @@ def get_args(argv=None):
     p.add_argument("--input_path", default=None, type=str)
     p.add_argument("--out_dir", default="inference_out", type=str)
     p.add_argument("--pretrained_weights", default="MeshAnything_350m.pth", type=str)
-    p.add_argument("--input_type", choices=["mesh", "pc_normal"], default="pc", help="Type of the asset to process (default: pc)")
+    p.add_argument("--input_type", choices=["mesh", "pc_normal", "pc_xyz"], default="pc", help="Type of the asset to process (default: pc)")
     p.add_argument("--codebook_size", default=8192, type=int)
     p.add_argument("--codebook_dim", default=1024, type=int)
     p.add_argument("--n_max_triangles", default=800, type=int)
@@ -48,7 +49,10 @@ def get_args(argv=None):
     p.add_argument("--synthetic_weights", default=False, action="store_true", help="seeded random checkpoint (no released file offline)")
     p.add_argument("--num_candidates", default=1, type=int,
                    help="with --sampling: draw this many meshes per input in one batch and keep the one closest to the input cloud")
+    p.add_argument("--normal_k", default=16, type=int, help="with --input_type pc_xyz: neighbours per point in the normal estimate (3..32)")
     args = p.parse_args(argv)
+    if not 3 <= args.normal_k <= 32:
+        p.error("--normal_k must be in 3..32")
     if args.num_candidates < 1:
         p.error("--num_candidates must be >= 1")
     if args.num_candidates > 1 and not args.sampling:
@@ -80,6 +84,8 @@ def main():
         input_list = sorted(os.listdir(args.input_dir))
         if args.input_type == "pc_normal":
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.endswith(".npy")]
+        elif args.input_type == "pc_xyz":
+            input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".npy", ".xyz", ".txt"))]
         else:                                    # main.py:125-128 keeps .ply / .obj / .npy for meshes; .npy is not a mesh file, .off / .stl are read too
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".ply", ".obj", ".off", ".stl"))]
     elif args.input_path is not None:
@@ -99,7 +105,7 @@ def main():
         pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True, device=sample_device)
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
-        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device)
+        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k)
 
     begin = time.time()
     print("Generation Start!!!")

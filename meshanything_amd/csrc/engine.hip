@@ -40,6 +40,7 @@
 #include "surface_sample.hpp"
 #include "watertight.hpp"
 #include "mesh_score.hpp"
+#include "pc_normals.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -905,6 +906,37 @@ int ma_op_score_meshes(const float* coords, int B, int F, const float* cloud, in
         if (!std::isfinite(mesh_scale) || !(mesh_scale > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: mesh_scale must be finite and > 0");
         if (ws_bytes < score::score_ws_bytes(B, F, P)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: workspace smaller than ma_score_meshes_workspace_bytes(B, F, P)");
         HIP_CHECK(score::launch_score_meshes(coords, B, F, cloud, cloud_ld, P, n_per_cloud, mesh_scale, scores, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- normals of a raw point cloud (csrc/pc_normals.hpp) -----------------------------------------------------------------------
+static bool pc_knn_shape_ok(int N, int Q, int k, int splits) {
+    return k >= MA_PC_KNN_MIN_K && k <= MA_PC_KNN_MAX_K && N >= k && N <= MA_PC_KNN_MAX_POINTS && Q >= 1 && Q <= MA_PC_KNN_MAX_QUERIES && splits >= 0 &&
+           splits <= MA_PC_KNN_MAX_SPLITS;
+}
+
+size_t ma_pc_knn_workspace_bytes(int N, int Q, int k, int splits) { return pc_knn_shape_ok(N, Q, k, splits) ? pcn::knn_ws_bytes(N, Q, k, splits) : 0; }
+
+int ma_op_pc_knn(const float* ref, int N, int ref_ld, const int32_t* query_idx, int Q, int k, int splits, int32_t* nbr_idx, float* nbr_d2, void* workspace,
+                 size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !nbr_idx || !nbr_d2 || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn: null pointer");
+        if (!pc_knn_shape_ok(N, Q, k, splits))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_knn: need 3 <= k <= 32, k <= N <= 2^22, 1 <= Q <= 2^20 and 0 <= splits <= 64");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn: ref_ld must be 3 or 6");
+        if (!query_idx && Q != N) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn: without query_idx every reference point is a query: Q must equal N");
+        if (ws_bytes < pcn::knn_ws_bytes(N, Q, k, splits)) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn: workspace smaller than ma_pc_knn_workspace_bytes(N, Q, k, splits)");
+        HIP_CHECK(pcn::launch_knn(ref, N, ref_ld, query_idx, Q, k, pcn::resolve_splits(N, Q, splits), nbr_idx, nbr_d2, workspace,
+                                  reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_normals(const float* ref, int N, int ref_ld, const int32_t* nbr_idx, int Q, int k, double* normals, double* eigvals, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !nbr_idx || !normals || !eigvals) throw MaError(MA_ERR_INVALID, "ma_op_pc_normals: null pointer");
+        if (!pc_knn_shape_ok(N, Q, k, 0)) throw MaError(MA_ERR_INVALID, "ma_op_pc_normals: need 3 <= k <= 32, k <= N <= 2^22 and 1 <= Q <= 2^20");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_normals: ref_ld must be 3 or 6");
+        HIP_CHECK(pcn::launch_normals(ref, N, ref_ld, nbr_idx, Q, k, normals, eigvals, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

@@ -1,4 +1,5 @@
-"""Input side of the hot path: the reference's `Dataset` (main.py:15-58) for point-cloud and mesh-file inputs."""
+"""Input side of the hot path: the reference's `Dataset` (main.py:15-58) for point-cloud and mesh-file inputs, and one input type the
+reference does not have: `pc_xyz`, a raw point cloud whose normals are estimated on the GPU (pc_normals.py)."""
 from __future__ import annotations
 
 import os
@@ -28,9 +29,16 @@ def uid_of(input_path: str) -> str:
 class Dataset:
     """`Dataset('pc_normal' | 'mesh', paths)` of main.py:15-58.  Sampling uses the GLOBAL numpy RNG like the reference
     (seed it first: main.py:129-133 calls accelerate.set_seed(args.seed) -> np.random.seed).  sample_device (e.g. "cuda"): sample
-    mesh inputs on that GPU (mesh_input.mesh_to_pc_normal(..., device=...)): the same draws, the same clouds."""
+    mesh inputs on that GPU (mesh_input.mesh_to_pc_normal(..., device=...)): the same draws, the same clouds.
 
-    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None):
+    `Dataset('pc_xyz', paths, normal_k=16)` has no reference counterpart: points without normals, from .npy files of shape (N, >= 3)
+    (only the first three columns are read, so the normals of an (N, 6) file are ignored) or .xyz / .txt files (np.loadtxt), N >=
+    n_points.  The same n_points rows as the pc_normal branch would draw are kept and their normals estimated from normal_k
+    neighbours on the GPU (pc_normals.xyz_to_pc_normal).  It is not called 'pc': that is the reference's command-line default, a type
+    its Dataset does not know and which therefore yields an empty dataset; that behaviour is restated here and pinned by the tests,
+    so the new type needs a name of its own."""
+
+    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16):
         self.data: List[Dict] = []
         if input_type == "pc_normal":
             for input_path in input_list:
@@ -49,6 +57,13 @@ class Dataset:
             for input_path in input_list:
                 vertices, faces = load_mesh(input_path)
                 self.data.append({"pc_normal": mesh_to_pc_normal(vertices, faces, n_points, device=sample_device), "uid": uid_of(input_path)})
+        elif input_type == "pc_xyz":
+            from .pc_normals import check_xyz, xyz_to_pc_normal
+            for input_path in input_list:
+                cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
+                cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
+                self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda"),
+                                  "uid": uid_of(input_path)})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
         print(f"dataset total data samples: {len(self.data)}")
 
