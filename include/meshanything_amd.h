@@ -220,6 +220,11 @@ MA_API int  ma_op_gemm(int wdtype, int impl, const float *A, int lda, const void
  * W (N, K) bf16; fp32 output C and / or bf16 output Cb (either may be NULL); K % 32 == 0, lda % 8 == 0, ld* % 4 == 0 */
 MA_API int  ma_op_gemm_bf16(const void *A, int lda, const void *W, const float *bias, const float *R, int ldr, float *C, int ldc,
                             void *Cb, int ldcb, int M, int N, int K, int act, void *stream);
+/* ... in one of its A/B forms (ma_op_gemm_bf16 runs the defaults): `variant` and `tile256` are what the engine options gemm_variant and gemm256 select, with
+ * the options' checks -- tile256 outside 0 .. 2 is MA_ERR_INVALID, a variant other than 6 MA_ERR_STATE unless the library was built with MA_EXPERIMENTAL=1.
+ * The kernel-level entry points belong to no engine: no engine's options reach them, and nothing set here reaches an engine. */
+MA_API int  ma_op_gemm_bf16_tuned(const void *A, int lda, const void *W, const float *bias, const float *R, int ldr, float *C, int ldc,
+                                  void *Cb, int ldcb, int M, int N, int K, int act, int variant, int tile256, void *stream);
 MA_API int  ma_op_layernorm(const float *x, int ldx, const float *g, const float *b, float eps, float *y, int ldy,
                             int rows, int D, void *stream);
 /* O[b,q,h*64+d] = softmax(Q K^T * scale) V, head_dim 64; strides in elements.  round_bf16: 0 fp32 tensors, exact fp32 kernel | 1 fp32 tensors

@@ -426,13 +426,22 @@ int ma_op_gemm(int wdtype, int impl, const float* A, int lda, const void* W, con
 // the bf16 policy's dense GEMM on its native operands (gemm_tile.hpp): A (M, lda) bf16, W (N, K) bf16; fp32 output C and / or bf16 output Cb
 int ma_op_gemm_bf16(const void* A, int lda, const void* W, const float* bias, const float* R, int ldr, float* C, int ldc, void* Cb, int ldcb, int M, int N,
                     int K, int act, void* stream) {
+    return ma_op_gemm_bf16_tuned(A, lda, W, bias, R, ldr, C, ldc, Cb, ldcb, M, N, K, act, GemmTune{}.variant, GemmTune{}.tile256, stream);
+}
+
+// ... in one of its A/B forms: what the engine options gemm_variant and gemm256 select, with their range and MA_EXPERIMENTAL checks
+int ma_op_gemm_bf16_tuned(const void* A, int lda, const void* W, const float* bias, const float* R, int ldr, float* C, int ldc, void* Cb, int ldcb, int M, int N,
+                          int K, int act, int variant, int tile256, void* stream) {
     return guarded(nullptr, [&] {
         if (!A || !W || (!C && !Cb)) throw MaError(MA_ERR_INVALID, "ma_op_gemm_bf16: null pointer");
+        check_value(find_option("gemm_variant", true), variant);
+        check_value(find_option("gemm256", true), tile256);
+        const GemmTune tune{variant, tile256};
         GemmTArgs t{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), bias, R, ldr, C, ldc, reinterpret_cast<bf16_t*>(Cb), ldcb, M, N, K, act};
         t.xcd_swizzle = 1;
         static int n_cus = -1;
         if (n_cus < 0) { int dev = 0; hipDeviceProp_t prop; n_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0; }
-        op_launched(H16_CALL(g_op_hdt, HT, launch_gemm_dense<HT>(t, n_cus, reinterpret_cast<hipStream_t>(stream))), "ma_op_gemm_bf16");
+        op_launched(H16_CALL(g_op_hdt, HT, launch_gemm_dense<HT>(t, n_cus, reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, tune)), "ma_op_gemm_bf16");
     });
 }
 

@@ -6,7 +6,7 @@
 
 namespace {
 
-int gemv_blocks(ma_engine* e, int N, int K) { return e->bf16 ? gemv_num_blocks<bf16_t>(N, K) : gemv_num_blocks<float>(N, K); }     // (the two 16-bit formats share their shapes)
+int gemv_blocks(ma_engine* e, int N, int K) { return e->bf16 ? gemv_num_blocks<bf16_t>(N, K, e->opt.gemv_tune()) : gemv_num_blocks<float>(N, K, e->opt.gemv_tune()); }     // (the two 16-bit formats share their shapes)
 
 // The values are part of the ABI: launch classes index ma_kernel_timing, trace kinds fill the `kinds` array of ma_trace_decode.
 enum LaunchClass { CLS_WEIGHTS = 0, CLS_ATTN = 1, CLS_PERSIST = 2, CLS_PICK = 3 };      // weight-streaming launches | attention, and launches that contain one | the persistent step | the pick
@@ -32,7 +32,7 @@ struct StepTimer {                    // launch filter (ma_profile_decode) / in-
 struct Rows { int r0 = 0, B = 1; };
 
 void gemv_launch(ma_engine* e, const GemvArgs& a, hipStream_t s, int B) {
-    launched(PREC_CALL(e->bf16, e->hdt, T, launch_gemv<T>(a, s, B)), "gemv");
+    launched(PREC_CALL(e->bf16, e->hdt, T, launch_gemv<T>(a, s, B, e->opt.gemv_tune())), "gemv");
 }
 
 bool use_mfma_decode(ma_engine* e, int B) { return e->bf16 && B >= e->opt.mfma_min_batch && B <= 64 && e->cfg.hidden % 128 == 0 && e->cfg.ffn % 128 == 0 && e->cfg.hidden <= 1024; }
@@ -152,7 +152,7 @@ struct Step {
     void gemm_dec(GemmDecArgs a, TraceKind kind) {
         if (!tm.on(CLS_WEIGHTS)) return;
         a.trace = tm.trace_slot(kind, (a.N + 15) / 16 * std::max(1, a.ksplit));
-        launched(H16_CALL(e->hdt, HT, launch_gemm_dec<HT>(a, s)), "gemm_dec");
+        launched(H16_CALL(e->hdt, HT, launch_gemm_dec<HT>(a, s, e->opt.mfma_chunks)), "gemm_dec");
     }
     // y2 of a layer as the LayerNorm 2 that follows reads it: fc2's partials + deferred epilogue, or one buffer
     ProIn y2_of(int l) const {
@@ -435,7 +435,7 @@ void gemv_chain(Step& p, const float* x0, bool head = true) {
 // changed (every loader clears embtab_ready; so do the setters that change that GEMV's shape: CLEARS_EMBTAB, engine_options.hpp); the
 // experimental persistent step reads the same table.
 void ensure_embtab(ma_engine* e, hipStream_t s) {
-    if (e->embtab_ready && e->embtab_small_rows == gemv_small_rows()) return;      // (gemv_small_rows is process-wide: another engine may have set it)
+    if (e->embtab_ready) return;
     const ma_config& c = e->cfg;
     const int rows_per_launch = 32768;                                             // grid.y
     for (int v0 = 0; v0 < c.codebook_size; v0 += rows_per_launch) {
@@ -447,7 +447,7 @@ void ensure_embtab(ma_engine* e, hipStream_t s) {
         gemv_launch(e, a, s, std::min(rows_per_launch, c.codebook_size - v0));
     }
     HIP_CHECK(hipStreamSynchronize(s));
-    e->embtab_ready = true; e->embtab_small_rows = gemv_small_rows();
+    e->embtab_ready = true;
 }
 // Where the step's embedding is gemv_kernel<..., EPI_EMBED> alone: the GEMV chain (batch 1 fused or five launches, rows in the grid) in every policy.
 // The matrix-core batches keep the launch: it also leaves the 16-bit operand of layer 0's q/k/v GEMM, and a launch is <= 0.6 % of their step.

@@ -53,7 +53,7 @@ struct Dense {
             t.R = o.R; t.ldr = o.ldr; t.C = out.c32; t.ldc = out.ld; t.Cb = reinterpret_cast<bf16_t*>(out.act); t.ldcb = out.ld;
             t.M = M; t.N = w.rows; t.K = w.cols; t.act = o.act; t.r_mod = o.r_mod; t.cmap = out.map; t.xcd_swizzle = e->opt.gemm_xcd_swizzle; t.part = o.part;
             if (o.kv) { t.kv_k = reinterpret_cast<bf16_t*>(o.kv->k); t.kv_v = reinterpret_cast<bf16_t*>(o.kv->v); t.kv_row_stride = o.kv->row_stride; t.kv_max_seq = o.kv->max_seq; t.kv_T = o.kv->T; t.kv_col0 = o.kv->col0; }
-            r = H16_CALL(e->hdt, HT, launch_gemm_dense<HT>(t, e->n_cus, s, o.kv ? &o.kv->rows_done : nullptr, o.sk, o.lnf));
+            r = H16_CALL(e->hdt, HT, launch_gemm_dense<HT>(t, e->n_cus, s, o.kv ? &o.kv->rows_done : nullptr, o.sk, o.lnf, e->opt.gemm_tune()));
         } else {
             if (o.part != 0) throw MaError(MA_ERR_INVALID, "internal: a GEMM by row parts needs a 16-bit phase");
             GemmArgs g{};

@@ -15,7 +15,7 @@ constexpr uint32_t from_to(int lo, int hi) { uint32_t m = 0; for (int v = lo; v 
 struct Opt {
     const char* name;
     int Options::* field;                    // where the value lives: a member of ma_engine::opt ...
-    void (*put)(ma_engine*, int64_t);        // ... or elsewhere (process-wide switches of the kernel headers, cfg, chain_resident); neither: read-only
+    void (*put)(ma_engine*, int64_t);        // ... or elsewhere (cfg, chain_resident); neither: read-only
     int64_t (*get)(ma_engine*);              // what is read back when that is not the stored value (elsewhere / effective / read-only)
     bool flag;                               // stored as value != 0
     uint32_t ok;                             // accepted values (0 = any), checked before `flag` is applied ...
@@ -47,10 +47,8 @@ const Opt OPTIONS[] = {
     // ---- dense phases
     {.name = "gemm_impl", .field = &Options::gemm_impl},
     {.name = "gemm_xcd_swizzle", .field = &Options::gemm_xcd_swizzle},
-    {.name = "gemm256", .put = [](ma_engine*, int64_t v) { gemm256_enabled() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemm256_enabled(); },
-     .ok = from_to(0, 2), .bad = "gemm256: 0 (128-row tiles), 1 (one tile per workgroup) or 2 (1 + the persistent form)"},
-    {.name = "gemm_variant", .put = [](ma_engine*, int64_t v) { gemm_tile_variant() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemm_tile_variant(); },
-     .product = [](int64_t v) { return v == 6; }, .needs_exp = "gemm_variant: the A/B tile variants need a library built with MA_EXPERIMENTAL=1"},
+    {.name = "gemm256", .field = &Options::gemm256, .ok = from_to(0, 2), .bad = "gemm256: 0 (128-row tiles), 1 (one tile per workgroup) or 2 (1 + the persistent form)"},
+    {.name = "gemm_variant", .field = &Options::gemm_variant, .product = [](int64_t v) { return v == 6; }, .needs_exp = "gemm_variant: the A/B tile variants need a library built with MA_EXPERIMENTAL=1"},
     {.name = "gemm_splitk", .field = &Options::gemm_splitk, .ok = from_to(0, 2), .bad = "gemm_splitk: 0 (never), 1 (fc2 of small prefills), 2 (+ out_proj)"},
     {.name = "attn_impl", .field = &Options::attn_impl, .ok = one_of(1, 2), .bad = "attn_impl: 1 (attn.hpp) or 2 (attn2.hpp)"},
     {.name = "qkv_to_cache", .field = &Options::qkv_to_cache, .flag = true},
@@ -68,13 +66,11 @@ const Opt OPTIONS[] = {
     // 0: never spin on other blocks (five-launch chain); 1: re-arm after a fallback, if the device allows
     {.name = "chain_resident", .put = [](ma_engine* e, int64_t v) { e->chain_resident = v != 0 && e->resident_blocks * 4 >= 256L * 5; },
      .get = [](ma_engine* e) -> int64_t { return e->chain_resident ? 1 : 0; }, .effects = DROPS_GRAPHS},
-    // ---- decode step, GEMV chain (the gemv_* switches are process-wide: gemv.hpp)
-    {.name = "gemv_rpw", .put = [](ma_engine*, int64_t v) { gemv_rpw_big() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemv_rpw_big(); },
-     .ok = one_of(1, 2, 4), .bad = "gemv_rpw must be 1, 2 or 4", .effects = DROPS_GRAPHS | RECOUNTS_PARTS},
-    {.name = "gemv_small_rows", .put = [](ma_engine*, int64_t v) { gemv_small_rows() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemv_small_rows(); },
-     .ok = one_of(0, 1, 2, 4), .bad = "gemv_small_rows must be 0, 1, 2 or 4", .effects = DROPS_GRAPHS | CLEARS_EMBTAB},
-    {.name = "gemv_k8_ksplit", .put = [](ma_engine*, int64_t v) { gemv_k8_ksplit() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemv_k8_ksplit(); },
-     .ok = one_of(1, 2, 4), .bad = "gemv_k8_ksplit must be 1, 2 or 4", .effects = DROPS_GRAPHS},
+    // ---- decode step, GEMV chain
+    {.name = "gemv_rpw", .field = &Options::gemv_rpw, .ok = one_of(1, 2, 4), .bad = "gemv_rpw must be 1, 2 or 4", .effects = DROPS_GRAPHS | RECOUNTS_PARTS},
+    {.name = "gemv_small_rows", .field = &Options::gemv_small_rows, .ok = one_of(0, 1, 2, 4), .bad = "gemv_small_rows must be 0, 1, 2 or 4",
+     .effects = DROPS_GRAPHS | CLEARS_EMBTAB},
+    {.name = "gemv_k8_ksplit", .field = &Options::gemv_k8_ksplit, .ok = one_of(1, 2, 4), .bad = "gemv_k8_ksplit must be 1, 2 or 4", .effects = DROPS_GRAPHS},
     // (the fused launches are read back as the engine will apply them: option AND eligibility)
     {.name = "fuse_qkv_attn", .field = &Options::fuse_qkv_attn, .get = [](ma_engine* e) -> int64_t { return fuse_qkv_attn(e) ? 1 : 0; }, .flag = true, .effects = DROPS_GRAPHS},
     {.name = "fuse_oproj_fc1", .field = &Options::fuse_oproj_fc1, .get = [](ma_engine* e) -> int64_t { return fuse_oproj_fc1(e) ? 1 : 0; }, .flag = true, .effects = DROPS_GRAPHS},
@@ -85,10 +81,9 @@ const Opt OPTIONS[] = {
     {.name = "embed_table", .field = &Options::embed_table, .get = [](ma_engine* e) -> int64_t { return embed_from_table(e, std::max(1, std::min(e->opt.profile_batch, e->cfg.max_batch))) ? 1 : 0; },
      .flag = true, .effects = DROPS_GRAPHS},
     {.name = "fuse_layer", .field = &Options::fuse_layer, .get = [](ma_engine* e) -> int64_t { return fuse_layer(e) ? 1 : 0; }, .product = zero_only, .needs_exp = "fuse_layer" MA_NEEDS_EXP, .effects = DROPS_GRAPHS},
-    // ---- decode step, matrix-core chain (mfma_chunks is process-wide: gemm_decode.hpp)
+    // ---- decode step, matrix-core chain
     {.name = "mfma_min_batch", .field = &Options::mfma_min_batch, .effects = DROPS_GRAPHS},
-    {.name = "mfma_chunks", .put = [](ma_engine*, int64_t v) { gemm_dec_chunks() = (int)v; }, .get = [](ma_engine*) -> int64_t { return gemm_dec_chunks(); },
-     .ok = one_of(4, 8), .bad = "mfma_chunks must be 4 or 8", .effects = DROPS_GRAPHS},
+    {.name = "mfma_chunks", .field = &Options::mfma_chunks, .ok = one_of(4, 8), .bad = "mfma_chunks must be 4 or 8", .effects = DROPS_GRAPHS},
     {.name = "mfma_fc2_ksplit", .field = &Options::mfma_fc2_ksplit, .ok = one_of(0, 1, 2, 4), .bad = "mfma_fc2_ksplit must be 0 (default), 1, 2 or 4",
      .extra = [](ma_engine* e, int64_t v) { if (v > 1 && e->cfg.ffn % (4 * (int)v * 32) != 0) throw MaError(MA_ERR_INVALID, "mfma_fc2_ksplit does not divide the ffn width"); }, .effects = DROPS_GRAPHS},
     {.name = "mfma_ln_waves", .field = &Options::mfma_ln_waves, .ok = one_of(0, 4, 8), .bad = "mfma_ln_waves must be 0 (by batch), 4 or 8", .effects = DROPS_GRAPHS},
@@ -130,10 +125,15 @@ const Opt& find_option(const std::string& n, bool to_set) {
     throw MaError(MA_ERR_INVALID, "unknown option " + n);
 }
 
-void set_option(ma_engine* e, const std::string& n, int64_t value) {
-    const Opt& o = find_option(n, true);
+// the refusals that need no engine (also those of ma_op_gemm_bf16_tuned's two switches)
+void check_value(const Opt& o, int64_t value) {
     if (!IS_EXPERIMENTAL && o.product && !o.product(value)) throw MaError(MA_ERR_STATE, o.needs_exp);
     if (o.ok && (value < 0 || value > 31 || !(o.ok >> value & 1u))) throw MaError(MA_ERR_INVALID, o.bad);
+}
+
+void set_option(ma_engine* e, const std::string& n, int64_t value) {
+    const Opt& o = find_option(n, true);
+    check_value(o, value);
     if (o.extra) o.extra(e, value);
     const int64_t v = o.flag ? (value != 0) : value;
     if (o.put) o.put(e, v); else e->opt.*(o.field) = (int)v;

@@ -157,6 +157,10 @@ struct ma_engine {
         int rows_mlp_ln2 = 1;            // rows_mlp.hpp step E: LayerNorm 2 finished in the MLP launch (the next q/k/v starts from 16-bit rows)
         int embed_table = 1;             // GEMV chain: the pick writes the next step's layer-0 input from the load-time table (misc.hpp pick_kernel<true>); 0: an embedding launch per step
         int gemm_xcd_swizzle = 1;        // dense GEMM: hand the tiles out XCD-aware (gemm_tile.hpp)
+        int gemm_variant = 6, gemm256 = 2, mfma_chunks = 8;             // GemmTune (gemm_tile.hpp): K-loop variant | 256 x 256 tiles | chunks in flight of the skinny GEMM at 33 .. 64 rows
+        int gemv_rpw = 4, gemv_small_rows = 1, gemv_k8_ksplit = 1;      // GemvTune (gemv.hpp): block shapes of the GEMV chain
+        GemmTune gemm_tune() const { return GemmTune{gemm_variant, gemm256, mfma_chunks}; }
+        GemvTune gemv_tune() const { return GemvTune{gemv_rpw, gemv_small_rows, gemv_k8_ksplit}; }
         int attn_impl = 2;               // bf16 dense attention: 2 = swapped-operand 32x32x16 kernel on packed V^T (attn2.hpp), 1 = attention_mfma_kernel (attn.hpp)
         int qkv_to_cache = 1;            // prefill (16-bit policies): the q|k|v GEMM writes K / V into the cache planes itself where it can (gemm256.hpp KV form); 0: always by kv_fill_rows_kernel (A/B)
         int gemm_splitk = 2;             // prefill fc2 (1) and out_proj (2, default) of small batches as 4 | 2 partial sums along K, added up by the LayerNorm that follows (0: never; A/B)
@@ -186,7 +190,7 @@ struct ma_engine {
     unsigned* d_pf_sink = nullptr;                 // (rows_mlp_prefetch)
     // embedding table (option embed_table; engine_decode.hpp ensure_embtab): read by the pick, and by the experimental persistent step
     float* d_embtab = nullptr;       // [codebook_size][hidden] fp32: input_layer(codebook row) + bias, built by the chain's own GEMV
-    bool embtab_ready = false; int embtab_small_rows = -1;      // ... for the weights in the arena, with this gemv_small_rows
+    bool embtab_ready = false;       // ... for the weights in the arena and this engine's gemv_small_rows
     // the persistent step's (MA_EXPERIMENTAL)
     DecLayerPtrs* d_layers = nullptr;
     u64* d_gran = nullptr; unsigned* d_serial = nullptr; unsigned* d_err = nullptr; unsigned* h_err = nullptr;

@@ -723,10 +723,6 @@ inline hipError_t g256_launch(const GemmTArgs& g, int nty, int ntx, hipStream_t 
     return hipGetLastError();
 }
 
-// engine option "gemm256" (default 2): 0 = the 128-row tiles only; 1 = the one-tile 256 x 256 kernel for the shapes it covers; 2 = 1 + the persistent
-// form for whole-tile 16-bit-output problems
-inline int& gemm256_enabled() { static int v = 2; return v; }
-
 // The dense GEMM of the 16-bit policies.  The big tile wants rounds of the chip (one block per CU) that are reasonably full: the matrix is cut along M into
 //   * the leading tile rows whose tiles fill their rounds to 60 % or more -- all whole tile rows when that holds (M = 64 x 257: 64 rows of 4 / 12 /
 //     16 tiles = 1 / 3 / 4 rounds; M = 16 x 257, N = 3072: 192 tiles = 0.75 round), else the largest count that makes exact rounds;
@@ -746,20 +742,20 @@ struct GemmSplitK { int max_parts = 1; long part_stride = 0; int parts = 1; int 
 // Cb its 16-bit copy.  On return `rows` = the leading rows for which the GEMM did it (the one-tile kernel's LNF form; 0: none) -- the caller runs the
 // row kernel over the rows behind them, whose plain sums were written to `tail_c` (same leading dimension as C) instead of C.
 struct GemmLnFuse { G256Ln ln; float* tail_c = nullptr; int rows = 0; };
-template <typename HT> inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf);
+template <typename HT> inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune);
 template <typename HT>
-inline hipError_t launch_gemm_dense(const GemmTArgs& g, int n_cus, hipStream_t s, int* kv_rows = nullptr, GemmSplitK* sk = nullptr, GemmLnFuse* lnf = nullptr) {
+inline hipError_t launch_gemm_dense(const GemmTArgs& g, int n_cus, hipStream_t s, int* kv_rows = nullptr, GemmSplitK* sk = nullptr, GemmLnFuse* lnf = nullptr, const GemmTune& tune = {}) {
     if (lnf && lnf->tail_c) {
         // every launch that does NOT finish the LayerNorm writes plain sums to the caller's tail buffer and no 16-bit copy (the caller's row kernel follows)
         GemmTArgs plain = g;
         plain.C = lnf->tail_c; plain.Cb = nullptr;
-        return launch_gemm_dense_impl<HT>(plain, g, n_cus, s, kv_rows, sk, lnf);
+        return launch_gemm_dense_impl<HT>(plain, g, n_cus, s, kv_rows, sk, lnf, tune);
     }
-    return launch_gemm_dense_impl<HT>(g, g, n_cus, s, kv_rows, sk, nullptr);
+    return launch_gemm_dense_impl<HT>(g, g, n_cus, s, kv_rows, sk, nullptr, tune);
 }
 // g: the arguments of the plain launches; g_ln: those of the LNF launch (outputs = the LayerNorm's)
 template <typename HT>
-inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf) {
+inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune) {
     if (kv_rows) *kv_rows = 0;
     if (sk) { sk->parts = 1; sk->rows = 0; }
     if (lnf) lnf->rows = 0;
@@ -776,19 +772,19 @@ inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_
             if (g.R) { d.res = g.R + r0 * g.ldr; d.res_stride = g.ldr; }
             if (g.C) { d.y = g.C + r0 * g.ldc; d.y_stride = g.ldc; }
             if (g.Cb) { d.yb = g.Cb + r0 * g.ldcb; d.yb_stride = g.ldcb; }
-            return launch_gemm_dec<HT>(d, s);
+            return launch_gemm_dec<HT>(d, s, tune.dec_chunks);
         }
         GemmTArgs t = g;
         t.A = g.A + r0 * g.lda; t.M = rows;
         if (g.R) t.R = g.R + r0 * g.ldr;
         t.C = g.C ? g.C + r0 * g.ldc : nullptr;
         t.Cb = g.Cb ? g.Cb + r0 * g.ldcb : nullptr;
-        return launch_gemm_tile<HT>(t, s, choice_rows);
+        return launch_gemm_tile<HT>(t, s, choice_rows, tune);
     };
     const int part = g.part;
     const int Mm = g.M - g.M % 256;                                  // parts 1 | 2 meet here
     if (part != 0 && (g.cmap.grp != 0 || g.r_mod != 0 || lnf)) return hipErrorInvalidValue;
-    if (tile256_ok && gemm256_enabled() && n_cus > 0 && g.K % 64 == 0 && g.K >= 128 && g.N >= 256 && g.M >= 256 && (long)((g.N + 255) / 256) * ((g.M + 255) / 256) < (1L << 24)) {
+    if (tile256_ok && tune.tile256 && n_cus > 0 && g.K % 64 == 0 && g.K >= 128 && g.N >= 256 && g.M >= 256 && (long)((g.N + 255) / 256) * ((g.M + 255) / 256) < (1L << 24)) {
         const int ntx = (g.N + 255) / 256;
         const bool can_split = g.cmap.grp == 0 && g.r_mod == 0;
         // (round 6: 60 % instead of 88 % + at least one whole round.  A tile of the big kernel now runs at ~1.2 PFLOP/s per CU-round against ~0.6 for the
@@ -797,7 +793,7 @@ inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_
         auto fills = [&](long tiles) { const long rounds = (tiles + n_cus - 1) / n_cus; return tiles * 100 >= rounds * n_cus * 60; };
         int nty = 0;                                                 // tile rows on the big tile
         int ks = 1;
-        if (sk && sk->max_parts >= 2 && gemm256_enabled() >= 2 && can_split && g.C && !g.Cb && g.act == ACT_NONE && g.N % 256 == 0 && g.K >= 1024 && !fills((long)ntx * (g.M / 256)) &&
+        if (sk && sk->max_parts >= 2 && tune.tile256 >= 2 && can_split && g.C && !g.Cb && g.act == ACT_NONE && g.N % 256 == 0 && g.K >= 1024 && !fills((long)ntx * (g.M / 256)) &&
             (long)ntx * (g.M / 256) >= 8) {
             // few tiles, long K: 4 (or 2) parts along K so that the launch comes to about one round (fc2 at 16 samples: 64 tiles x 4 = one round of 16 K-tiles
             // instead of a quarter round of 64)
@@ -828,12 +824,12 @@ inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_
             m.M = can_split ? nty * 256 : g.M;
             // whole tiles with 16-bit output: the persistent form (next tile's operands requested before this tile's epilogue; its 4-KB-patch epilogue is
             // the faster one even where every workgroup has a single tile)
-            const bool persist = gemm256_enabled() >= 2 && can_split && !g.C && g.Cb && !g.R && g.N % 256 == 0 && n_cus >= 8;
+            const bool persist = tune.tile256 >= 2 && can_split && !g.C && g.Cb && !g.R && g.N % 256 == 0 && n_cus >= 8;
             // (measured and not kept, round 6: at 64 samples out_proj / fc2 with the LayerNorm inside took 79 / 158 us against 42 + 30 / 124 + 30 us for GEMM +
             //  row kernel -- the epilogue holds the 128 x 64 sums of a wave in registers across two exchanges (97 dwords per lane spilled) and every tile row
             //  waits for its slowest tile twice; profiles/r06_ab_layernorm_in_gemm.txt.  Compiled with MA_EXPERIMENTAL=1 only.)
 #ifdef MA_EXPERIMENTAL
-            const bool do_ln = lnf && ks == 1 && gemm256_enabled() >= 2 && can_split && g.C && g.act == ACT_NONE && g.N % 256 == 0 && lnf->ln.gran && lnf->ln.gamma && lnf->ln.beta &&
+            const bool do_ln = lnf && ks == 1 && tune.tile256 >= 2 && can_split && g.C && g.act == ACT_NONE && g.N % 256 == 0 && lnf->ln.gran && lnf->ln.gamma && lnf->ln.beta &&
                                lnf->ln.err && lnf->ln.epoch != 0 && g_ln.C && g_ln.ldc % 4 == 0 && (!g_ln.Cb || g_ln.ldcb % 4 == 0);
             if (do_ln && part != 2) {
                 lnf->rows = nty * 256;
@@ -871,7 +867,7 @@ inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_
     }
     if (part == 1) return Mm > 0 ? rows_on_small(0, Mm, false, g.M) : hipSuccess;
     if (part == 2) return g.M > Mm ? rows_on_small((size_t)Mm, g.M - Mm, false, g.M) : hipSuccess;
-    return launch_gemm_tile<HT>(g, s);
+    return launch_gemm_tile<HT>(g, s, 0, tune);
 }
 
 }  // namespace ma

@@ -199,11 +199,14 @@ MA_NO_ASAN __global__ __launch_bounds__(WM * WN * 64) void gemm_tile_kernel(Gemm
     }
 }
 
-// variant knob (engine option gemm_variant; only libraries built with MA_EXPERIMENTAL=1 honour values other than the default 6; A/B in
+// What the engine options gemm_variant / gemm256 / mfma_chunks choose between (host side only: it travels beside GemmTArgs).
+// variant (engine option gemm_variant; only libraries built with MA_EXPERIMENTAL=1 honour values other than the default 6; A/B in
 // profiles/): 0 = K-tile 64, 2 stages | 1 = K-tile 32, 4 stages | 2 = K-tile 32, 5 stages |
 // 3 = K-tile 64, 3 stages (one block per CU) | 4 = K-tile 64, 3 stages, raw barrier | 5 = K-tile 32, 4 stages, raw barrier | 6 = K-tile 64,
 // 2 stages, raw barrier (default) | 7 = K-tile 32, 6 stages, raw barrier | 8 = the 128 x 64 tile for every shape (A/B of the tail rounds)
-inline int& gemm_tile_variant() { static int v = 6; return v; }      // 6: +2 ... +13 % over 0 on the path's shapes (profiles/r03_ab_dense_attention_gemm_variants.txt)
+// tile256 (gemm256.hpp): 0 = the 128-row tiles only; 1 = the one-tile 256 x 256 kernel for the shapes it covers; 2 = 1 + the persistent form for whole-tile
+// 16-bit-output problems | dec_chunks: of the skinny GEMM that computes a tail of <= 64 rows (gemm_decode.hpp launch_gemm_dec)
+struct GemmTune { int variant = 6, tile256 = 2, dec_chunks = 8; };      // variant 6: +2 ... +13 % over 0 on the path's shapes (profiles/r03_ab_dense_attention_gemm_variants.txt)
 
 template <typename HT, int BM, int BN, int BK, int NS, bool RAW = false, int WM = 2, int WN = 2>
 inline hipError_t gt_launch(const GemmTArgs& g, hipStream_t s) {
@@ -222,12 +225,12 @@ inline hipError_t gt_launch(const GemmTArgs& g, hipStream_t s) {
 // choice_rows > 0: the tile shape is chosen as for a problem of that many rows (a stretch of a larger problem's rows computed by a call of its own gets the
 // larger problem's kernel, hence its bits: launch_gemm_dense, GemmTArgs::part); the grid always comes from the real row count
 template <typename HT>
-inline hipError_t launch_gemm_tile(const GemmTArgs& g, hipStream_t s, int choice_rows = 0) {
+inline hipError_t launch_gemm_tile(const GemmTArgs& g, hipStream_t s, int choice_rows = 0, const GemmTune& tune = {}) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     const int Msel = choice_rows > 0 ? choice_rows : g.M;
     if (g.K % 32 != 0 || g.lda % 8 != 0 || (g.C && g.ldc % 4) || (g.R && g.ldr % 4) || (g.Cb && g.ldcb % 4) || (!g.C && !g.Cb)) return hipErrorInvalidValue;
     const long tiles128 = (long)((g.N + 127) / 128) * ((Msel + 127) / 128);
-    const int v = gemm_tile_variant();
+    const int v = tune.variant;
 #ifdef MA_EXPERIMENTAL
     // the A/B variants of rounds 2-3 (profiles/r02_ab_gemm_tile_stages.txt, r03_ab_gemm_tile_occupancy_and_tail.txt): evidence, not product
     if (v == 8 && g.K % 64 == 0 && g.M > 64 && g.N > 32) return gt_launch<HT, 128, 64, 64, 2, true>(g, s);      // the half tile everywhere

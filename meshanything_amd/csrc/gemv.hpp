@@ -307,37 +307,40 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
 
 // ---- host-side dispatch ------------------------------------------------------------------------------------------
 struct GemvShape { int ksplit, lpl, rpw; };
-// rows per wave for the big matrices (engine option "gemv_rpw"): 1 = most blocks ... 4 = a quarter of the blocks / input copies
-// (default 4: measured 1.4 % (2 vs 1) + 0.5 % (4 vs 2) faster per decode step, profiles/r01_ab_rows_per_wave.txt)
-inline int& gemv_rpw_big() { static int v = 4; return v; }
-// N <= 2048, K = 2 pieces (out_proj, embed): 0 = two waves split K, one row per group (512 blocks at N = 1024);
-// r > 0 = one wave per r whole rows (4 r rows per block: fewer blocks repeat the prologue -- out_proj's merges 67 KB of partials).
-// Default 1 (256 blocks): decode step 519.6 -> 491.7 us at kv 300 (profiles/r02_ab_oproj_block_shape.txt)
-inline int& gemv_small_rows() { static int v = 1; return v; }
-// K = 8 pieces (fc2): waves that split K (4 = 1024 blocks at N = 1024, each staging the 16 KB input; 2; 1 = one wave per row, 256 blocks).
-// Default 1: 494.2 -> 483.0 us (profiles/r02_ab_fc2_block_shape.txt)
-inline int& gemv_k8_ksplit() { static int v = 1; return v; }
+// the block shapes the engine options gemv_rpw / gemv_small_rows / gemv_k8_ksplit choose between (host side only: it travels beside GemvArgs)
+struct GemvTune {
+    // rows per wave for the big matrices: 1 = most blocks ... 4 = a quarter of the blocks / input copies
+    // (default 4: measured 1.4 % (2 vs 1) + 0.5 % (4 vs 2) faster per decode step, profiles/r01_ab_rows_per_wave.txt)
+    int rpw_big = 4;
+    // N <= 2048, K = 2 pieces (out_proj, embed): 0 = two waves split K, one row per group (512 blocks at N = 1024);
+    // r > 0 = one wave per r whole rows (4 r rows per block: fewer blocks repeat the prologue -- out_proj's merges 67 KB of partials).
+    // Default 1 (256 blocks): decode step 519.6 -> 491.7 us at kv 300 (profiles/r02_ab_oproj_block_shape.txt)
+    int small_rows = 1;
+    // K = 8 pieces (fc2): waves that split K (4 = 1024 blocks at N = 1024, each staging the 16 KB input; 2; 1 = one wave per row, 256 blocks).
+    // Default 1: 494.2 -> 483.0 us (profiles/r02_ab_fc2_block_shape.txt)
+    int k8_ksplit = 1;
+};
 
 template <typename WT>
-inline GemvShape gemv_shape(int N, int K) {
+inline GemvShape gemv_shape(int N, int K, const GemvTune& tune = {}) {
     constexpr int VEC = WTraits<WT>::VEC;
     if (K % (64 * VEC) != 0) return {1, 0, 1};
     const int nc = K / (64 * VEC);                       // 16-byte pieces per lane for one row
-    const int rpw = N >= 2048 ? gemv_rpw_big() : 1;
+    const int rpw = N >= 2048 ? tune.rpw_big : 1;
     switch (nc) {
         case 1: return {1, 1, rpw > 2 ? 2 : rpw};
         // > 1024 blocks do not fit the chip at once (8195 lm_head rows: 2049 blocks start over 2.9 us): two rows per wave
-        case 2: return N <= 2048 ? (gemv_small_rows() > 0 ? GemvShape{1, 2, gemv_small_rows()} : GemvShape{2, 1, 1}) : GemvShape{1, 2, N > 4096 ? (rpw > 2 ? rpw : 2) : rpw};
+        case 2: return N <= 2048 ? (tune.small_rows > 0 ? GemvShape{1, 2, tune.small_rows} : GemvShape{2, 1, 1}) : GemvShape{1, 2, N > 4096 ? (rpw > 2 ? rpw : 2) : rpw};
         case 4: return {2, 2, N > 4096 ? 2 : (rpw > 2 ? 2 : rpw)};
-        case 8: return gemv_k8_ksplit() == 1 ? GemvShape{1, 8, 1} : gemv_k8_ksplit() == 2 ? GemvShape{2, 4, 1} : GemvShape{4, 2, 1};
+        case 8: return tune.k8_ksplit == 1 ? GemvShape{1, 8, 1} : tune.k8_ksplit == 2 ? GemvShape{2, 4, 1} : GemvShape{4, 2, 1};
         case 16: return {4, 4, 1};
         default: return {1, 0, 1};
     }
 }
 template <typename WT>
-inline int gemv_rows_per_block(int N, int K) { const GemvShape g = gemv_shape<WT>(N, K); return (4 / g.ksplit) * g.rpw; }
+inline int gemv_rows_per_block(int N, int K, const GemvTune& tune = {}) { const GemvShape g = gemv_shape<WT>(N, K, tune); return (4 / g.ksplit) * g.rpw; }
 template <typename WT>
-inline int gemv_num_blocks(int N, int K) { const int rpb = gemv_rows_per_block<WT>(N, K); return (N + rpb - 1) / rpb; }
+inline int gemv_num_blocks(int N, int K, const GemvTune& tune = {}) { const int rpb = gemv_rows_per_block<WT>(N, K, tune); return (N + rpb - 1) / rpb; }
 
 template <typename WT, int KS, int LP, int RW>
 inline void launch_gemv_pro(const GemvArgs& a, int pro, dim3 grid, hipStream_t s) {
@@ -348,12 +351,12 @@ inline void launch_gemv_pro(const GemvArgs& a, int pro, dim3 grid, hipStream_t s
 }
 
 template <typename WT>
-inline hipError_t launch_gemv(const GemvArgs& a, hipStream_t s, int batch = 1) {
+inline hipError_t launch_gemv(const GemvArgs& a, hipStream_t s, int batch = 1, const GemvTune& tune = {}) {
     constexpr int VEC = WTraits<WT>::VEC;
     if (a.K % VEC != 0) return hipErrorInvalidValue;
     const int pro = a.attn_ws ? PRO_ATTN : (a.ln_g ? PRO_LN : PRO_PLAIN);
     if (pro == PRO_ATTN && (a.K != a.attn_heads * 64)) return hipErrorInvalidValue;
-    GemvShape g = gemv_shape<WT>(a.N, a.K);
+    GemvShape g = gemv_shape<WT>(a.N, a.K, tune);
     if (pro == PRO_ATTN && g.lpl > 0 && a.K > 1024) g = GemvShape{1, 0, 1};       // wide merges take the generic path
     const int rpb = (4 / g.ksplit) * g.rpw;
     const dim3 grid((a.N + rpb - 1) / rpb, batch);

@@ -21,8 +21,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from meshanything_amd import _lib                                   # noqa: E402
-from meshanything_amd.config import MAConfig, DTYPE_BF16           # noqa: E402
-from meshanything_amd.engine import Engine                          # noqa: E402
 
 SHAPES = [(16448, 1024, 1024, 0, True, "f32"), (16448, 3072, 1024, 0, False, "bf16"), (16448, 4096, 1024, 1, False, "bf16"),
           (16448, 1024, 4096, 0, True, "f32"), (67648, 768, 768, 2, False, "both"), (8192, 8192, 512, 0, False, "bf16"),
@@ -38,8 +36,6 @@ def main():
     per_case = int(sys.argv[1]) if len(sys.argv) > 1 else 600
     lib = _lib.load()
     print(lib.ma_version().decode(), "| MA_DEBUG =", os.environ.get("MA_DEBUG", ""), "| device", torch.cuda.get_device_name(0), flush=True)
-    eng = Engine(MAConfig.tiny(dtype=DTYPE_BF16))
-    eng.set_option("gemm256", 2)
     main_s = torch.cuda.current_stream()
     side, copy_s = torch.cuda.Stream(), torch.cuda.Stream()
     src = torch.empty(1 << 28, dtype=torch.uint8, device="cuda").random_(0, 255)

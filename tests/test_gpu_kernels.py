@@ -56,6 +56,17 @@ def h16(request, lib):
     lib.ma_op_set_half_dtype(1)
 
 
+@pytest.fixture(scope="module")
+def experimental(lib):
+    """Was the library built with MA_EXPERIMENTAL=1?  (a read-only engine option: one engine for the module asks)"""
+    from meshanything_amd.config import MAConfig, DTYPE_BF16
+    from meshanything_amd.engine import Engine
+    eng = Engine(MAConfig.tiny(dtype=DTYPE_BF16))
+    exp = bool(eng.get_option("experimental"))
+    eng.close()
+    return exp
+
+
 def _p(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -527,18 +538,13 @@ def test_rows_prologue(lib, h16, B, pro):
                                                    (257, 2304, 768, 0, False, "bf16"), (130, 200, 192, 0, True, "both"), (1, 1024, 768, 0, False, "f32"),
                                                    (16912, 768, 3072, 0, True, "f32"), (300, 64, 768, 0, False, "f32"), (77, 1152, 96, 0, False, "f32")])
 @pytest.mark.parametrize("variant", [0, 6, 12, 13], ids=["syncthreads", "rawbarrier", "tile256x128", "tile256x128s3"])
-def test_gemm_bf16_tile(lib, h16, M, N, K, act, use_res, out, variant):
+def test_gemm_bf16_tile(lib, h16, experimental, M, N, K, act, use_res, out, variant):
     """The bf16 policy's dense GEMM (gemm_tile.hpp) on its native bf16 operands at the batched dense-phase shapes (B x 257,
     B x 4096, B x 1057 rows), ragged edges, both tile variants; fp32 and bf16 outputs; reports TFLOP/s.  variant: the K-loop's
     barrier form and tile (engine option gemm_variant: 0 = __syncthreads(), 6 = counted vmcnt + raw s_barrier with the per-shape tile choice
     of launch_gemm_tile, the default; 12 / 13 = the 8-wave 256 x 128 tile with two / three LDS stages everywhere)."""
-    from meshanything_amd.config import MAConfig, DTYPE_BF16
-    from meshanything_amd.engine import Engine
-    knob = Engine(MAConfig.tiny(dtype=DTYPE_BF16))                      # gemm_variant is a process-wide knob behind an engine option
-    if variant != 6 and (not knob.get_option("experimental") or h16.name == "fp16"):
-        knob.close()
+    if variant != 6 and (not experimental or h16.name == "fp16"):
         pytest.skip("the A/B tile variants live in libraries built with MA_EXPERIMENTAL=1 (and are exercised in bf16 there)")
-    knob.set_option("gemm_variant", variant)
     g = _gen(M + 3 * N + 5 * K)
     A = (torch.randn(M, K, generator=g) + torch.linspace(-1, 1, K)[None, :] * 0.5).to(h16.tdt)
     W = (torch.randn(N, K, generator=g) / math.sqrt(K) + torch.linspace(0, 1, N)[:, None] * 0.02).to(h16.tdt)
@@ -558,7 +564,7 @@ def test_gemm_bf16_tile(lib, h16, M, N, K, act, use_res, out, variant):
     Cb = torch.zeros(M, N, dtype=h16.tdt, device=dev) if out in ("bf16", "both") else None
 
     def run():
-        _chk(lib, lib.ma_op_gemm_bf16(_p(Ad), K, _p(Wd), _p(bd), _p(Rd) if use_res else None, N, _p(C), N, _p(Cb), N, M, N, K, act, _stream()))
+        _chk(lib, lib.ma_op_gemm_bf16_tuned(_p(Ad), K, _p(Wd), _p(bd), _p(Rd) if use_res else None, N, _p(C), N, _p(Cb), N, M, N, K, act, variant, 2, _stream()))
     run()
     torch.cuda.synchronize()
     scale = max(1e-6, float(ref.abs().max()))
@@ -580,8 +586,6 @@ def test_gemm_bf16_tile(lib, h16, M, N, K, act, use_res, out, variant):
         torch.cuda.synchronize()
         us = ev[0].elapsed_time(ev[1]) / 20 * 1e3
         print(f"[gemm_tile, variant {variant}] M {M} N {N} K {K} act {act} res {use_res} out {out}: {us:.1f} us = {2.0 * M * N * K / us * 1e-6:.1f} TFLOP/s")
-    knob.set_option("gemm_variant", 6)
-    knob.close()
 
 
 @pytest.mark.parametrize("M,N,K,act,use_res,out", [(16448, 1024, 1024, 0, True, "f32"), (16448, 3072, 1024, 0, False, "bf16"), (16448, 4096, 1024, 1, False, "bf16"),
@@ -593,9 +597,6 @@ def test_gemm_256_tile(lib, h16, M, N, K, act, use_res, out):
     rows: whole rounds on the big tile + the remainder on 128 x 128 tiles), M = 64 x 1057, ragged M and N edges, K = 64 (one K-tile: prologue only)
     and K = 128 -- against fp64 torch; bit-stable across launches (its in-flight LDS-DMA schedule is timing dependent, its result must not be);
     A/B timing against the 128-row tiles it replaces."""
-    from meshanything_amd.config import MAConfig, DTYPE_BF16
-    from meshanything_amd.engine import Engine
-    knob = Engine(MAConfig.tiny(dtype=DTYPE_BF16))                      # gemm256 is a process-wide knob behind an engine option
     g = _gen(M + 3 * N + 5 * K)
     A = (torch.randn(M, K, generator=g) + torch.linspace(-1, 1, K)[None, :] * 0.5).to(h16.tdt)
     W = (torch.randn(N, K, generator=g) / math.sqrt(K) + torch.linspace(0, 1, N)[:, None] * 0.02).to(h16.tdt)
@@ -612,10 +613,9 @@ def test_gemm_256_tile(lib, h16, M, N, K, act, use_res, out):
     scale = max(1e-6, float(ref.abs().max()))
 
     def run(Cf, Cb):
-        _chk(lib, lib.ma_op_gemm_bf16(_p(A), K, _p(W), _p(bias), _p(R), N, _p(Cf), N, _p(Cb), N, M, N, K, act, _stream()))
+        _chk(lib, lib.ma_op_gemm_bf16_tuned(_p(A), K, _p(W), _p(bias), _p(R), N, _p(Cf), N, _p(Cb), N, M, N, K, act, 6, mode, _stream()))
     res = {}
     for mode in (2, 1, 0, 2):                            # 2: + the persistent form where it applies (whole-tile 16-bit output, more than one round)
-        knob.set_option("gemm256", mode)
         Cf = torch.full((M, N), float("nan")) if out in ("f32", "both") else None
         Cb = torch.zeros(M, N, dtype=h16.tdt) if out in ("bf16", "both") else None
         run(Cf, Cb)
@@ -655,5 +655,3 @@ def test_gemm_256_tile(lib, h16, M, N, K, act, use_res, out):
     fl = 2.0 * M * N * K
     print(f"[gemm256 {h16.name}] M {M} N {N} K {K} act {act} res {use_res} out {out}: default (persistent where it applies) {res[('us', 2)]:.1f} us = {fl / res[('us', 2)] * 1e-6:.1f} TFLOP/s | "
           f"one tile per workgroup {res[('us', 1)]:.1f} us = {fl / res[('us', 1)] * 1e-6:.1f} | 128-row tiles {res[('us', 0)]:.1f} us = {fl / res[('us', 0)] * 1e-6:.1f} | ratio {res[('us', 0)] / res[('us', 2)]:.2f}x")
-    knob.set_option("gemm256", 2)
-    knob.close()

@@ -26,12 +26,12 @@ LISTED = {"mfma_fc2_ksplit": (0, (1, 2, 0), (-1, 3), "mfma_fc2_ksplit must be 0 
           "prefill_tail": (2, (0, 1, 2), (-1, 3), "prefill_tail: 0 (one stream), 1 (the last rows as a chain on a second stream), 2 (... of the lowest priority)"),
           "gemm_splitk": (2, (0, 1, 2), (-1, 3), "gemm_splitk: 0 (never), 1 (fc2 of small prefills), 2 (+ out_proj)"),
           "gemm256": (2, (0, 1, 2), (-1, 3), "gemm256: 0 (128-row tiles), 1 (one tile per workgroup) or 2 (1 + the persistent form)"),
-          "attn_impl": (2, (1, 2), (0, 3), "attn_impl: 1 (attn.hpp) or 2 (attn2.hpp)")}
+          "attn_impl": (2, (1, 2), (0, 3), "attn_impl: 1 (attn.hpp) or 2 (attn2.hpp)"),
+          "gemv_rpw": (4, (1, 2, 4), (0, 3), "gemv_rpw must be 1, 2 or 4"),
+          "gemv_small_rows": (1, (0, 2, 4, 1), (-1, 3), "gemv_small_rows must be 0, 1, 2 or 4"),
+          "gemv_k8_ksplit": (1, (2, 4, 1), (0, 3), "gemv_k8_ksplit must be 1, 2 or 4")}
 # can be set, and the parent cannot read them back (a library that can returns the stored value): name: (accepted, refused, message)
-WRITE_ONLY = {"gemm_impl": ((1, 0), (), ""), "prefill_stepwise": ((1, 0), (), ""), "profile_batch": ((8, 1), (), ""),
-              "gemv_rpw": ((1, 2, 4), (0, 3), "gemv_rpw must be 1, 2 or 4"),
-              "gemv_small_rows": ((0, 2, 4, 1), (-1, 3), "gemv_small_rows must be 0, 1, 2 or 4"),
-              "gemv_k8_ksplit": ((2, 4, 1), (0, 3), "gemv_k8_ksplit must be 1, 2 or 4")}
+WRITE_ONLY = {"gemm_impl": ((1, 0), (), ""), "prefill_stepwise": ((1, 0), (), ""), "profile_batch": ((8, 1), (), "")}
 # stored as value != 0, read back as stored
 FLAGS = {"rows_mlp_ln2": 1, "qkv_xcd_local": 1, "qkv_to_cache": 1}
 # stored as value != 0 (default 1), read back as the engine will apply them: option AND eligibility
@@ -39,12 +39,6 @@ EFFECTIVE = ("fuse_qkv_attn", "fuse_oproj_fc1", "fuse_rows_attn", "fuse_rows_mlp
 READ_ONLY = ("experimental", "persist_available", "chain_fallbacks", "xchg_last_code", "xchg_timeouts", "slow_blocks", "slow_block_max_us",
              "scalar_sweep_rescues", "xchg_first_giveup_code", "xchg_first_giveup_block", "xchg_first_giveup_polls", "xchg_descheduled",
              "resident_blocks", "dense_rows")
-PROCESS_WIDE = {"gemm256": 2, "gemm_variant": 6, "mfma_chunks": 8, "gemv_rpw": 4, "gemv_small_rows": 1, "gemv_k8_ksplit": 1}
-
-
-def _restore(eng):
-    for k, v in PROCESS_WIDE.items():
-        eng.set_option(k, v)
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +50,6 @@ def tiny():
     try:
         yield eng
     finally:
-        _restore(eng)
         eng.close()
 
 
@@ -69,7 +62,6 @@ def full8():
     try:
         yield eng
     finally:
-        _restore(eng)
         eng.close()
 
 
@@ -89,103 +81,100 @@ def test_defaults_values_and_refusals(tiny):
     eng = tiny
     exp = eng.get_option("experimental")
     assert exp in (0, 1)
-    try:
-        for name, (default, values) in PLAIN.items():
-            assert eng.get_option(name) == default, name
-            for v in values + (default,):
-                eng.set_option(name, v)
-                assert eng.get_option(name) == v, (name, v)
-        for name, (default, values, bad, msg) in LISTED.items():
-            assert eng.get_option(name) == default, name
-            for v in bad:
-                _refused(eng, name, v, INVALID, msg)
-                assert eng.get_option(name) == default, (name, v)
-            for v in values:
-                eng.set_option(name, v)
-                assert eng.get_option(name) == v, (name, v)
-        # (a split of fc2 along K must divide the ffn width into whole 128-column pieces: 4 does not at this shape's 256)
-        assert tiny.cfg.ffn % (4 * 4 * 32) != 0
-        _refused(eng, "mfma_fc2_ksplit", 4, INVALID, "mfma_fc2_ksplit does not divide the ffn width")
-        for name, (values, bad, msg) in WRITE_ONLY.items():
-            for v in bad:
-                _refused(eng, name, v, INVALID, msg)
-            for v in values:
-                eng.set_option(name, v)
-                try:
-                    got = eng.get_option(name)
-                except MAError as e:
-                    assert e.code == INVALID and ("unknown option " + name) in str(e)
-                else:
-                    assert got == v, (name, v)
-        for name, default in FLAGS.items():
-            assert eng.get_option(name) == default, name
-            for v, want in ((0, 0), (2, 1), (-1, 1), (1, 1)):
-                eng.set_option(name, v)
-                assert eng.get_option(name) == want, (name, v)
-        # decode_groups: read back as the number of groups a batch of profile_batch rows is cut into (every group keeps >= 4 rows)
-        assert eng.get_option("decode_groups") == 1
-        for v in (0, 17):
-            _refused(eng, "decode_groups", v, INVALID, "decode_groups: 1 .. 16")
-        eng.set_option("profile_batch", 16)
-        for v in range(1, 17):
-            eng.set_option("decode_groups", v)
-            assert eng.get_option("decode_groups") == min(v, 4), v
-        eng.set_option("profile_batch", 1)
-        assert eng.get_option("decode_groups") == 1
-        eng.set_option("decode_groups", 1)
-        # rows_attn_early: 0 .. 6; the placements that were measured and not kept live in MA_EXPERIMENTAL libraries only
-        assert eng.get_option("rows_attn_early") == 6
-        for v in (-1, 7):
-            _refused(eng, "rows_attn_early", v, INVALID, "rows_attn_early: 0 .. 6")
-        for v in (0, 1, 2, 3, 4, 5, 6):
-            if not exp and v in (0, 1, 2, 4):
-                _refused(eng, "rows_attn_early", v, STATE, "rows_attn_early: placements 0, 1, 2 and 4 need a library built with MA_EXPERIMENTAL=1 (measured, not kept)")
-                continue
-            eng.set_option("rows_attn_early", v)
-            assert eng.get_option("rows_attn_early") == v
-        # gemm_variant: any value in an MA_EXPERIMENTAL library, 6 (the default) otherwise
-        assert eng.get_option("gemm_variant") == 6
-        for v in (5, 7, 0):
-            if exp:
-                eng.set_option("gemm_variant", v)
-                assert eng.get_option("gemm_variant") == v
+    for name, (default, values) in PLAIN.items():
+        assert eng.get_option(name) == default, name
+        for v in values + (default,):
+            eng.set_option(name, v)
+            assert eng.get_option(name) == v, (name, v)
+    for name, (default, values, bad, msg) in LISTED.items():
+        assert eng.get_option(name) == default, name
+        for v in bad:
+            _refused(eng, name, v, INVALID, msg)
+            assert eng.get_option(name) == default, (name, v)
+        for v in values:
+            eng.set_option(name, v)
+            assert eng.get_option(name) == v, (name, v)
+    # (a split of fc2 along K must divide the ffn width into whole 128-column pieces: 4 does not at this shape's 256)
+    assert tiny.cfg.ffn % (4 * 4 * 32) != 0
+    _refused(eng, "mfma_fc2_ksplit", 4, INVALID, "mfma_fc2_ksplit does not divide the ffn width")
+    for name, (values, bad, msg) in WRITE_ONLY.items():
+        for v in bad:
+            _refused(eng, name, v, INVALID, msg)
+        for v in values:
+            eng.set_option(name, v)
+            try:
+                got = eng.get_option(name)
+            except MAError as e:
+                assert e.code == INVALID and ("unknown option " + name) in str(e)
             else:
-                _refused(eng, "gemm_variant", v, STATE, "gemm_variant: the A/B tile variants need a library built with MA_EXPERIMENTAL=1")
-        eng.set_option("gemm_variant", 6)
-        assert eng.get_option("gemm_variant") == 6
-        # the rejected decode-step forms
-        assert eng.get_option("decode_impl") == 0 and eng.get_option("rows_fused") == 0 and eng.get_option("fuse_layer") == 0 and eng.get_option("fuse_ln") == 0
-        for name in ("rows_fused", "fuse_layer", "decode_impl", "fuse_ln"):
-            eng.set_option(name, 0)
-            assert eng.get_option(name) == 0
+                assert got == v, (name, v)
+    for name, default in FLAGS.items():
+        assert eng.get_option(name) == default, name
+        for v, want in ((0, 0), (2, 1), (-1, 1), (1, 1)):
+            eng.set_option(name, v)
+            assert eng.get_option(name) == want, (name, v)
+    # decode_groups: read back as the number of groups a batch of profile_batch rows is cut into (every group keeps >= 4 rows)
+    assert eng.get_option("decode_groups") == 1
+    for v in (0, 17):
+        _refused(eng, "decode_groups", v, INVALID, "decode_groups: 1 .. 16")
+    eng.set_option("profile_batch", 16)
+    for v in range(1, 17):
+        eng.set_option("decode_groups", v)
+        assert eng.get_option("decode_groups") == min(v, 4), v
+    eng.set_option("profile_batch", 1)
+    assert eng.get_option("decode_groups") == 1
+    eng.set_option("decode_groups", 1)
+    # rows_attn_early: 0 .. 6; the placements that were measured and not kept live in MA_EXPERIMENTAL libraries only
+    assert eng.get_option("rows_attn_early") == 6
+    for v in (-1, 7):
+        _refused(eng, "rows_attn_early", v, INVALID, "rows_attn_early: 0 .. 6")
+    for v in (0, 1, 2, 3, 4, 5, 6):
+        if not exp and v in (0, 1, 2, 4):
+            _refused(eng, "rows_attn_early", v, STATE, "rows_attn_early: placements 0, 1, 2 and 4 need a library built with MA_EXPERIMENTAL=1 (measured, not kept)")
+            continue
+        eng.set_option("rows_attn_early", v)
+        assert eng.get_option("rows_attn_early") == v
+    # gemm_variant: any value in an MA_EXPERIMENTAL library, 6 (the default) otherwise
+    assert eng.get_option("gemm_variant") == 6
+    for v in (5, 7, 0):
         if exp:
-            _refused(eng, "decode_impl", 2, INVALID, "decode_impl must be 0 (launch chain) or 1 (persistent step)")
-            _refused(eng, "decode_impl", -1, INVALID, "decode_impl must be 0 (launch chain) or 1 (persistent step)")
-            eng.set_option("decode_impl", 1)
-            assert eng.get_option("decode_impl") == 1
-            eng.set_option("decode_impl", 0)
+            eng.set_option("gemm_variant", v)
+            assert eng.get_option("gemm_variant") == v
         else:
-            for name in ("rows_fused", "fuse_layer", "decode_impl"):
-                for v in (1, -1, 2):
-                    _refused(eng, name, v, STATE, name + NEEDS_EXP)
-            for v in (1, -1):
-                _refused(eng, "fuse_ln", v, STATE, "fuse_ln needs a library built with MA_EXPERIMENTAL=1 (LayerNorm inside the GEMM epilogue: measured, not kept)")
-        # chain_resident: 0 switches the in-launch exchanges off; non-zero arms them where the device can hold the fused grids
-        can = 1 if eng.get_option("resident_blocks") * 4 >= 256 * 5 else 0
-        assert eng.get_option("chain_resident") == can
-        for v, want in ((0, 0), (1, can), (5, can)):
-            eng.set_option("chain_resident", v)
-            assert eng.get_option("chain_resident") == want
-        # names nobody knows, names that can only be read
-        _unknown(eng, lambda: eng.set_option("no_such_option", 1), "no_such_option")
-        _unknown(eng, lambda: eng.get_option("no_such_option"), "no_such_option")
-        for name in READ_ONLY:
-            before = eng.get_option(name)
-            _unknown(eng, lambda: eng.set_option(name, 1), name)
-            assert eng.get_option(name) == before, name
-        assert eng.get_option("dense_rows") == 16 and eng.get_option("chain_fallbacks") == 0 and eng.get_option("xchg_timeouts") == 0
-    finally:
-        _restore(eng)
+            _refused(eng, "gemm_variant", v, STATE, "gemm_variant: the A/B tile variants need a library built with MA_EXPERIMENTAL=1")
+    eng.set_option("gemm_variant", 6)
+    assert eng.get_option("gemm_variant") == 6
+    # the rejected decode-step forms
+    assert eng.get_option("decode_impl") == 0 and eng.get_option("rows_fused") == 0 and eng.get_option("fuse_layer") == 0 and eng.get_option("fuse_ln") == 0
+    for name in ("rows_fused", "fuse_layer", "decode_impl", "fuse_ln"):
+        eng.set_option(name, 0)
+        assert eng.get_option(name) == 0
+    if exp:
+        _refused(eng, "decode_impl", 2, INVALID, "decode_impl must be 0 (launch chain) or 1 (persistent step)")
+        _refused(eng, "decode_impl", -1, INVALID, "decode_impl must be 0 (launch chain) or 1 (persistent step)")
+        eng.set_option("decode_impl", 1)
+        assert eng.get_option("decode_impl") == 1
+        eng.set_option("decode_impl", 0)
+    else:
+        for name in ("rows_fused", "fuse_layer", "decode_impl"):
+            for v in (1, -1, 2):
+                _refused(eng, name, v, STATE, name + NEEDS_EXP)
+        for v in (1, -1):
+            _refused(eng, "fuse_ln", v, STATE, "fuse_ln needs a library built with MA_EXPERIMENTAL=1 (LayerNorm inside the GEMM epilogue: measured, not kept)")
+    # chain_resident: 0 switches the in-launch exchanges off; non-zero arms them where the device can hold the fused grids
+    can = 1 if eng.get_option("resident_blocks") * 4 >= 256 * 5 else 0
+    assert eng.get_option("chain_resident") == can
+    for v, want in ((0, 0), (1, can), (5, can)):
+        eng.set_option("chain_resident", v)
+        assert eng.get_option("chain_resident") == want
+    # names nobody knows, names that can only be read
+    _unknown(eng, lambda: eng.set_option("no_such_option", 1), "no_such_option")
+    _unknown(eng, lambda: eng.get_option("no_such_option"), "no_such_option")
+    for name in READ_ONLY:
+        before = eng.get_option(name)
+        _unknown(eng, lambda: eng.set_option(name, 1), name)
+        assert eng.get_option(name) == before, name
+    assert eng.get_option("dense_rows") == 16 and eng.get_option("chain_fallbacks") == 0 and eng.get_option("xchg_timeouts") == 0
 
 
 def test_effective_values_at_the_350m_shape(full8):
@@ -269,7 +258,6 @@ def test_setters_drop_the_captured_steps(tiny):
     finally:
         eng.set_option("use_graph", 1)
         eng.set_option("mfma_min_batch", 4)
-        _restore(eng)
 
 
 def test_gemv_rpw_recaptures_the_step_at_the_350m_shape(full8, golden_dir):
@@ -281,13 +269,10 @@ def test_gemv_rpw_recaptures_the_step_at_the_350m_shape(full8, golden_dir):
     want, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
     want = want.cpu()
     assert len(set(want[0].tolist())) > 8
-    try:
-        for name, there, back, same_there in (("gemv_rpw", 2, 4, True), ("gemv_rpw", 1, 4, True), ("gemv_small_rows", 2, 1, False), ("gemv_k8_ksplit", 2, 1, False)):
-            eng.set_option(name, there)
-            got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
-            assert got.shape == want.shape and (not same_there or torch.equal(got.cpu(), want)), (name, there)
-            eng.set_option(name, back)
-            got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
-            assert torch.equal(got.cpu(), want), (name, "back to", back)
-    finally:
-        _restore(eng)
+    for name, there, back, same_there in (("gemv_rpw", 2, 4, True), ("gemv_rpw", 1, 4, True), ("gemv_small_rows", 2, 1, False), ("gemv_k8_ksplit", 2, 1, False)):
+        eng.set_option(name, there)
+        got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
+        assert got.shape == want.shape and (not same_there or torch.equal(got.cpu(), want)), (name, there)
+        eng.set_option(name, back)
+        got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
+        assert torch.equal(got.cpu(), want), (name, "back to", back)
