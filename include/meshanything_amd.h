@@ -415,6 +415,36 @@ MA_API int    ma_op_score_meshes(const float *coords, int B, int F, const float 
                                  float *scores, void *workspace, size_t ws_bytes, void *stream);
 MA_API size_t ma_score_meshes_workspace_bytes(int B, int F, int P);
 
+/* ---- agreement of a candidate mesh's face normals with the cloud's normals (csrc/mesh_normals.hpp): the normal-consistency term of
+ * best-of-N sampling and the winding of the written faces.  Has no reference counterpart (the reference hands the cloud's normals to the
+ * encoder and never reads them again; its winding comes from trimesh's fix_normals).  Needs no engine; errors via ma_last_error(NULL);
+ * every argument is checked before the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`.
+ *
+ * ma_op_mesh_normals: coords, cloud, n_per_cloud and mesh_scale as for ma_op_score_meshes, except that cloud_ld must be 6: columns 0..2
+ *   are xyz, columns 3..5 the normal, used as given (not re-normalised; finite values are the caller's duty).  Per valid face f with the
+ *   scaled vertices A, B, C, all fp32 and without FMA contraction, so that a float32 restatement that rounds every operation gives the same bits:
+ *     n = (B - A) x (C - A), l2 = n . n; the face is measurable when l2 is finite and > 0, then nh = n / sqrtf(l2)
+ *     q_0..q_6 = A, B, C, the midpoints of AB, BC, CA, the centroid (the quadrature points of ma_op_score_meshes)
+ *     j_k = the cloud index p that minimises the pair (d, p), d = fl(fl(dx * dx + dy * dy) + dz * dz), dx = fl(q_k.x - x_p), ...: a total
+ *           order, the lowest index wins ties; a NaN or +inf key never wins, so j_k is always in 0 .. P - 1 (0 when every key is)
+ *     t_k = fl(fl(nh.x * m.x + nh.y * m.y) + nh.z * m.z), m = the normal of cloud row j_k
+ *     a_f = (t_0 + ... + t_6, in that order) * fl(1/7)          signed agreement; < 0: the face is wound against the cloud
+ *     u_f = (|t_0| + ... + |t_6|) * fl(1/7)                     unsigned consistency, independent of the winding
+ *     area_f = 0.5 * sqrtf(l2), the area ma_op_score_meshes uses; a face that is not measurable has a_f = u_f = area_f = 0 and adds
+ *              nothing below
+ *   face_agree (B, F) fp32 = a_f, 0 for an invalid or not measurable face.  nscores (B, 4) fp32:
+ *     [0] NC = sum_f area_f * u_f / sum_f area_f over the measurable faces       [1] the share of that area whose a_f < 0
+ *     [2] sum_f area_f over the measurable faces (at most FLT_MAX)               [3] the number of valid faces
+ *   [0] = [1] = 0 (the worst NC) without a measurable face; no output is NaN or infinite.  The cloud -> mesh direction of normal
+ *   consistency is not computed: the nearest face of a point is tied between the faces of a shared edge.
+ *   Bitwise reproducible, and a candidate's numbers do not depend on B or (nscores) on NaN rows between its valid faces: the per-face terms
+ *   are summed in fp64 in the fixed order of ma_op_score_meshes; no float atomics.  workspace: face_abs (B, F) fp32 = u_f | face_area
+ *   (B, F) fp32, -1 = invalid face, 0 = not measurable | nn_idx (B, F, 7) int32 = j_k, -1 = invalid face; each part aligned to 256 bytes.
+ *   Limits as for ma_op_score_meshes.  workspace: ma_mesh_normals_workspace_bytes(B, F) bytes of device memory (0 outside the limits). */
+MA_API int    ma_op_mesh_normals(const float *coords, int B, int F, const float *cloud, int cloud_ld, int P, int n_per_cloud, float mesh_scale,
+                                 float *face_agree, float *nscores, void *workspace, size_t ws_bytes, void *stream);
+MA_API size_t ma_mesh_normals_workspace_bytes(int B, int F);
+
 /* ---- normals of a raw point cloud, for --input_type pc_xyz (csrc/pc_normals.hpp).  Has no reference counterpart: the reference takes only
  * clouds that already carry unit normals (pc_normal), or meshes.  Needs no engine; errors via ma_last_error(NULL); every argument is
  * checked before the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`.  No atomics: bitwise reproducible.

@@ -12,7 +12,9 @@ HIP kernels, `meshanything_amd/surface_sample.py`), `--mc` makes the input water
 (`meshanything_amd/watertight.py`: unsigned distance + marching cubes in HIP instead of mesh2sdf + scikit-image); the
 mesh clean-up of main.py:156-175 is restated without trimesh in `meshanything_amd/mesh_export.py`.  One flag the reference does
 not have: `--sampling --num_candidates N` draws N meshes per input in one batch and writes the one closest to the input cloud
-(`meshanything_amd/mesh_score.py`).  And one input type it does not have: `--input_type pc_xyz` takes points WITHOUT normals (.npy of
+(`meshanything_amd/mesh_score.py`); `--normal_weight W` adds W * (1 - normal consistency between the candidate's faces and the cloud's
+normals) to that ranking, and `--orient cloud` winds every written face the way the nearest cloud normals face instead of by
+`fix_normals`' signed volume (`--orient volume`, the default and the reference's behaviour).  And one input type it does not have: `--input_type pc_xyz` takes points WITHOUT normals (.npy of
 shape (N, >= 3), .xyz or .txt) and estimates them on the GPU from `--normal_k` neighbours (`meshanything_amd/pc_normals.py`).
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
@@ -50,6 +52,10 @@ def get_args(argv=None):
     p.add_argument("--num_candidates", default=1, type=int,
                    help="with --sampling: draw this many meshes per input in one batch and keep the one closest to the input cloud")
     p.add_argument("--normal_k", default=16, type=int, help="with --input_type pc_xyz: neighbours per point in the normal estimate (3..32)")
+    p.add_argument("--normal_weight", default=0.0, type=float,
+                   help="with --num_candidates > 1: add this times (1 - normal consistency with the cloud's normals) to a candidate's total")
+    p.add_argument("--orient", default="volume", choices=["volume", "cloud"],
+                   help="winding of the written faces: by signed volume (fix_normals, the reference) or by the cloud's normals")
     args = p.parse_args(argv)
     if not 3 <= args.normal_k <= 32:
         p.error("--normal_k must be in 3..32")
@@ -57,6 +63,10 @@ def get_args(argv=None):
         p.error("--num_candidates must be >= 1")
     if args.num_candidates > 1 and not args.sampling:
         p.error("--num_candidates > 1 needs --sampling (greedy candidates are identical)")
+    if not (0.0 <= args.normal_weight < float("inf")):
+        p.error("--normal_weight must be finite and >= 0")
+    if args.normal_weight > 0 and args.num_candidates < 2:
+        p.error("--normal_weight > 0 needs --num_candidates > 1")
     return args
 
 
@@ -113,16 +123,20 @@ def main():
     for batch in dp.batches(mine, args.batchsize_per_gpu):
         data = [dataset[i] for i in batch]
         pc = torch.from_numpy(np.stack([d["pc_normal"] for d in data])).cuda()
+        orient = "cloud" if args.orient == "cloud" else None
         if args.num_candidates > 1:
-            det = model.forward_detailed(pc, sampling=True, num_candidates=args.num_candidates)
+            det = model.forward_detailed(pc, sampling=True, num_candidates=args.num_candidates, normal_weight=args.normal_weight, orient=orient)
             outputs = det["coords"].cpu().numpy()
-            for d, c, tot in zip(data, det["chosen"].tolist(), det["total"].tolist()):
-                print(f'{d["uid"]}: candidate {c} of {args.num_candidates} chosen, totals ' + " ".join(f"{t:.6f}" for t in tot))
+            ncs = det["normal_scores"][..., 0].tolist() if args.normal_weight > 0 else [None] * len(data)
+            for d, c, tot, nc in zip(data, det["chosen"].tolist(), det["total"].tolist(), ncs):
+                line = f'{d["uid"]}: candidate {c} of {args.num_candidates} chosen, totals ' + " ".join(f"{t:.6f}" for t in tot)
+                print(line if nc is None else line + ", NC " + " ".join(f"{v:.6f}" for v in nc))
         else:
-            outputs = model(pc, sampling=args.sampling).cpu().numpy()
+            outputs = model(pc, sampling=args.sampling, orient=orient).cpu().numpy()
         for d, coords in zip(data, outputs):
             verts, faces = faces_from_coords(coords)
-            faces = fix_normals(verts, faces)
+            if orient is None:                       # --orient cloud: the winding came with the coordinates
+                faces = fix_normals(verts, faces)
             path = os.path.join(out_dir, f'{d["uid"]}_gen.obj')
             write_obj(path, verts, faces)
             print(f"{path} Over!!")

@@ -112,6 +112,8 @@ SIGNATURES = {
     "ma_f64_to_f16": (_I, [_P, C.c_int64, _P]),
     "ma_op_score_meshes": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _P, C.c_size_t, _P]),
     "ma_score_meshes_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "ma_op_mesh_normals": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, C.c_size_t, _P]),
+    "ma_mesh_normals_workspace_bytes": (C.c_size_t, [_I, _I]),
     "ma_op_pc_knn": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_knn_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "ma_op_pc_normals": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),

@@ -39,6 +39,7 @@
 #include "state.hpp"
 #include "surface_sample.hpp"
 #include "watertight.hpp"
+#include "mesh_normals.hpp"
 #include "mesh_score.hpp"
 #include "pc_normals.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
@@ -915,6 +916,25 @@ int ma_op_score_meshes(const float* coords, int B, int F, const float* cloud, in
         if (!std::isfinite(mesh_scale) || !(mesh_scale > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: mesh_scale must be finite and > 0");
         if (ws_bytes < score::score_ws_bytes(B, F, P)) throw MaError(MA_ERR_INVALID, "ma_op_score_meshes: workspace smaller than ma_score_meshes_workspace_bytes(B, F, P)");
         HIP_CHECK(score::launch_score_meshes(coords, B, F, cloud, cloud_ld, P, n_per_cloud, mesh_scale, scores, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- normal agreement of candidate meshes with their cloud (csrc/mesh_normals.hpp) --------------------------------------------
+static bool mesh_normals_shape_ok(int B, int F) { return B >= 1 && F >= 1 && F <= MA_SCORE_MESHES_MAX_FACES; }
+
+size_t ma_mesh_normals_workspace_bytes(int B, int F) { return mesh_normals_shape_ok(B, F) ? mnorm::normals_ws_bytes(B, F) : 0; }
+
+int ma_op_mesh_normals(const float* coords, int B, int F, const float* cloud, int cloud_ld, int P, int n_per_cloud, float mesh_scale, float* face_agree,
+                       float* nscores, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!coords || !cloud || !face_agree || !nscores || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: null pointer");
+        if (!score_shape_ok(B, F, P)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: need B >= 1, 1 <= F <= 2^20 and 1 <= P <= 2^20");
+        if (n_per_cloud < 1 || B % n_per_cloud) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: n_per_cloud must be >= 1 and divide B");
+        if (cloud_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: cloud_ld must be 6 (xyz and the normal)");
+        if (!std::isfinite(mesh_scale) || !(mesh_scale > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: mesh_scale must be finite and > 0");
+        if (ws_bytes < mnorm::normals_ws_bytes(B, F)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: workspace smaller than ma_mesh_normals_workspace_bytes(B, F)");
+        HIP_CHECK(mnorm::launch_mesh_normals(coords, B, F, cloud, cloud_ld, P, n_per_cloud, mesh_scale, face_agree, nscores, workspace,
+                                             reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

@@ -20,7 +20,8 @@ weights), `.codebook_size`, `.codebook_dim`, `.n_max_triangles` (meshanything.py
 `.dtype` ("bf16" | "fp16" | "fp32"), `.batchsize_per_gpu` and `.num_candidates` (engine max_batch = their product), `.device` (GPU index).
 
 Not in the reference: `model(pc_normal, sampling=True, num_candidates=N)` draws N meshes per cloud in one batch and returns the one
-closest to its cloud (mesh_score.py).
+closest to its cloud (mesh_score.py); `normal_weight=w` adds w * (1 - normal consistency) to that ranking and
+`orient="cloud"` winds every returned face the way the cloud's normals face.
 """
 from __future__ import annotations
 
@@ -164,31 +165,51 @@ class MeshAnything(torch.nn.Module):
         return z ^ (z >> 31)
 
     @torch.no_grad()
-    def forward(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, num_candidates: int = 1) -> torch.Tensor:
+    def forward(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, num_candidates: int = 1,
+                normal_weight: float = 0.0, orient: Optional[str] = None) -> torch.Tensor:
         """(B, 4096, 6) -> (B, n_max_triangles, 3, 3) fp32, NaN rows = invalid faces (meshanything.py:134-176): one library call.
         `seed` (optional) pins the sampler's uniform stream for this call; by default it advances from call to call.
-        `num_candidates` N > 1 (needs sampling): N meshes per cloud, the one closest to its cloud is returned (forward_detailed)."""
-        return self.forward_detailed(pc_normal, sampling, seed=seed, num_candidates=num_candidates)["coords"]
+        `num_candidates` N > 1 (needs sampling): N meshes per cloud, the one closest to its cloud is returned (forward_detailed);
+        `normal_weight` and `orient`: forward_detailed."""
+        return self.forward_detailed(pc_normal, sampling, seed=seed, num_candidates=num_candidates, normal_weight=normal_weight,
+                                     orient=orient)["coords"]
 
     @torch.no_grad()
     def forward_detailed(self, pc_normal: torch.Tensor, sampling: bool = False, seed: Optional[int] = None, num_candidates: int = 1,
-                         **kw) -> Dict[str, object]:
+                         normal_weight: float = 0.0, orient: Optional[str] = None, **kw) -> Dict[str, object]:
         """forward() plus the intermediate tensors (tokens, lengths, ids, latents) for tests and tooling.  With num_candidates N > 1:
         coords (G, F, 3, 3) = the chosen candidate of each cloud, candidates (G, N, F, 3, 3), scores (G, N, 4) (mesh_score.score_meshes;
-        `mesh_scale` may be passed), total (G, N), chosen (G,), and tokens, lengths, ids, latents of all G * N rows (row g * N + i)."""
+        `mesh_scale` may be passed), total (G, N), chosen (G,), and tokens, lengths, ids, latents of all G * N rows (row g * N + i).
+        normal_weight w > 0 (needs N > 1): total = the distance term + w * (1 - NC) with normal_scores (G, N, 4) of
+        mesh_score.normal_agreement, returned too.  orient="cloud": every face of coords is wound the way the cloud's normals face
+        (mesh_score.orient_faces); face_agree (G, F) is the signed agreement of the returned mesh's faces as measured before that
+        (candidates stay as decoded).  With the defaults neither op is called."""
         n = int(num_candidates)
+        w = float(normal_weight)
         if n < 1:
             raise ValueError(f"num_candidates must be >= 1, got {num_candidates}")
+        if not (0.0 <= w < float("inf")):
+            raise ValueError(f"normal_weight must be finite and >= 0, got {normal_weight}")
+        if w > 0 and n < 2:
+            raise ValueError("normal_weight > 0 needs num_candidates > 1: one candidate has nothing to be ranked against")
+        if orient not in (None, "cloud"):
+            raise ValueError(f'orient must be None or "cloud", got {orient!r}')
         if n > 1:
-            return self._best_of_n(pc_normal, bool(sampling), seed, n, **kw)
+            return self._best_of_n(pc_normal, bool(sampling), seed, n, normal_weight=w, orient=orient, **kw)
+        mesh_scale = kw.pop("mesh_scale", None) if orient else None
         s = self._next_stream_seed() if seed is None else int(seed)
-        return self.engine.forward(pc_normal, sampling=bool(sampling), seed=s, **kw)
+        out = self.engine.forward(pc_normal, sampling=bool(sampling), seed=s, **kw)
+        if orient:
+            from .mesh_score import DEFAULT_MESH_SCALE, normal_agreement, orient_faces
+            _, agree = normal_agreement(out["coords"], pc_normal, 1, DEFAULT_MESH_SCALE if mesh_scale is None else mesh_scale)
+            out["coords"], out["face_agree"] = orient_faces(out["coords"], agree), agree
+        return out
 
     def _best_of_n(self, pc_normal: torch.Tensor, sampling: bool, seed: Optional[int], n: int, mesh_scale: Optional[float] = None,
-                   **kw) -> Dict[str, object]:
+                   normal_weight: float = 0.0, orient: Optional[str] = None, **kw) -> Dict[str, object]:
         """Encode the G clouds once, decode G * n rows in one generate() -- the sampler's uniform stream is keyed by (seed, row, step), so
         the rows of a group differ --, detokenize, score every row against its cloud on the GPU and keep the best of each group."""
-        from .mesh_score import DEFAULT_MESH_SCALE, score_meshes, select
+        from .mesh_score import DEFAULT_MESH_SCALE, normal_agreement, orient_faces, score_meshes, select
         if not sampling:
             raise ValueError("num_candidates > 1 needs sampling=True: greedy candidates are identical")
         G = pc_normal.shape[0]
@@ -196,15 +217,29 @@ class MeshAnything(torch.nn.Module):
             raise ValueError(f"{G} clouds x num_candidates {n} = {G * n} rows exceed the engine's max_batch {self.cfg.max_batch} "
                              f"(= batchsize_per_gpu * num_candidates the model was built with)")
         s = self._next_stream_seed() if seed is None else int(seed)
+        scale = DEFAULT_MESH_SCALE if mesh_scale is None else mesh_scale
         eng = self.engine
         latents, prefix = eng.encode(pc_normal)
         latents = latents.repeat_interleave(n, dim=0)
         tokens, lengths = eng.generate(prefix.repeat_interleave(n, dim=0), sampling=True, seed=s, **kw)
         ids = eng.postprocess_tokens(tokens)
         cand = eng.detokenize(ids, latents)
-        scores = score_meshes(cand, pc_normal.to(cand.device), n, DEFAULT_MESH_SCALE if mesh_scale is None else mesh_scale)
-        chosen, total = select(scores, n)
+        cloud = pc_normal.to(cand.device)
+        scores = score_meshes(cand, cloud, n, scale)
+        extra = {}
+        agree = None
+        if normal_weight > 0:
+            nscores, agree = normal_agreement(cand, cloud, n, scale)
+            chosen, total = select(scores, n, nscores, normal_weight)
+            extra["normal_scores"] = nscores.view(G, n, 4)
+        else:
+            chosen, total = select(scores, n)
+        rows = torch.arange(G, device=cand.device)
         cand = cand.view(G, n, *cand.shape[1:])
-        coords = cand[torch.arange(G, device=cand.device), chosen]
+        coords = cand[rows, chosen]
+        if orient:
+            # the chosen rows' agreement: taken from the batch when it was scored, else measured on the G chosen meshes alone
+            agree = agree.view(G, n, -1)[rows, chosen] if agree is not None else normal_agreement(coords, cloud, 1, scale)[1]
+            coords, extra["face_agree"] = orient_faces(coords, agree), agree
         return {"coords": coords, "candidates": cand, "scores": scores.view(G, n, 4), "total": total, "chosen": chosen, "tokens": tokens,
-                "lengths": lengths, "ids": ids, "latents": latents}
+                "lengths": lengths, "ids": ids, "latents": latents, **extra}
