@@ -477,6 +477,34 @@ MA_API size_t ma_pc_knn_workspace_bytes(int N, int Q, int k, int splits);
 MA_API int    ma_op_pc_normals(const float *ref, int N, int ref_ld, const int32_t *nbr_idx, int Q, int k, double *normals, double *eigvals,
                                void *stream);
 
+/* ---- farthest-point sampling of a point cloud, for --point_sampling fps (csrc/pc_fps.hpp).  Has no reference counterpart: the reference
+ * keeps np.random.choice(N, n, replace=False) rows.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before
+ * the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`; the host reads nothing back between the picks.
+ * No atomics, and no workgroup waits for another inside a launch: bitwise reproducible.
+ *
+ * ma_op_pc_fps: n of the N rows of ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6: idx (n) int32 in pick order and
+ *   d2 (n) fp32.  With p_i the xyz of row i and
+ *       key(a, b) = fl32(fl32(dx * dx + dy * dy) + dz * dz),  dx = fl32(a.x - b.x), dy = fl32(a.y - b.y), dz = fl32(a.z - b.z)
+ *   (the key of ma_op_pc_knn, no FMA contraction):  m_i = +inf for every i; for t = 0 .. n - 1:  idx[t] = s_t;  d2[t] = m_{s_t} (+inf
+ *   at t = 0);  m_i = min(m_i, key(p_i, p_{s_t})) for every i;  m_{s_t} = -1, so a picked row is never picked again (duplicates of it
+ *   are ordinary points);  s_{t+1} = the i of greatest m_i, the lowest index among equals.  s_0 = start, a row in [0, N); with start =
+ *   -1 it is the row farthest from the bounding box's centre: per axis lo = min, hi = max, c = fl32(fl32(lo + hi) * 0.5), s_0 = the i of
+ *   greatest key(p_i, c), the lowest index among equals -- deterministic, no random numbers.  It follows that the n indices are
+ *   distinct for any N >= n, that d2[1:] is non-increasing, exactly, and that after n picks every row lies within sqrt(d2[n - 1]) of a
+ *   picked one.  A numpy float32 restatement gives the same indices and the same bits.  Non-finite coordinates: unspecified picks,
+ *   every index in [0, N), nothing read or written out of bounds.
+ *   form: 1 = one workgroup keeps the cloud in registers for all n picks, one launch, N <= MA_PC_FPS_ONE_MAX_POINTS (a larger N is an
+ *   error); 2 = one launch per pick over many workgroups, any N; 0 = the implementation's choice, a function of N alone.  The result
+ *   does not depend on form, bit for bit.
+ *   1 <= n <= N <= MA_PC_FPS_MAX_POINTS, n <= MA_PC_FPS_MAX_PICKS.  workspace: ma_pc_fps_workspace_bytes(N, n, form) bytes of device
+ *   memory (0 for arguments outside those limits); its contents on entry do not matter. */
+#define MA_PC_FPS_MAX_POINTS (1 << 22)
+#define MA_PC_FPS_MAX_PICKS  (1 << 16)
+#define MA_PC_FPS_ONE_MAX_POINTS (1 << 14)
+MA_API int    ma_op_pc_fps(const float *ref, int N, int ref_ld, int n, int start, int form, int32_t *idx, float *d2, void *workspace,
+                           size_t ws_bytes, void *stream);
+MA_API size_t ma_pc_fps_workspace_bytes(int N, int n, int form);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ not have: `--sampling --num_candidates N` draws N meshes per input in one batch 
 normals) to that ranking, and `--orient cloud` winds every written face the way the nearest cloud normals face instead of by
 `fix_normals`' signed volume (`--orient volume`, the default and the reference's behaviour).  And one input type it does not have: `--input_type pc_xyz` takes points WITHOUT normals (.npy of
 shape (N, >= 3), .xyz or .txt) and estimates them on the GPU from `--normal_k` neighbours (`meshanything_amd/pc_normals.py`).
+`--point_sampling fps` (with pc_normal and pc_xyz) keeps the 4096 points farthest-point sampling picks on the GPU
+(`meshanything_amd/pc_fps.py`) instead of the reference's uniform draw; such an input consumes no draws from the numpy RNG, so the RNG
+state later stages see differs from a `--point_sampling random` run.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -56,7 +59,11 @@ def get_args(argv=None):
                    help="with --num_candidates > 1: add this times (1 - normal consistency with the cloud's normals) to a candidate's total")
     p.add_argument("--orient", default="volume", choices=["volume", "cloud"],
                    help="winding of the written faces: by signed volume (fix_normals, the reference) or by the cloud's normals")
+    p.add_argument("--point_sampling", default="random", choices=["random", "fps"],
+                   help="with --input_type pc_normal / pc_xyz: which 4096 rows of the input to keep: a uniform draw (the reference) or farthest-point sampling on the GPU")
     args = p.parse_args(argv)
+    if args.point_sampling == "fps" and args.input_type == "mesh":
+        p.error("--point_sampling fps applies to --input_type pc_normal and pc_xyz, not to mesh inputs")
     if not 3 <= args.normal_k <= 32:
         p.error("--normal_k must be in 3..32")
     if args.num_candidates < 1:
@@ -115,7 +122,7 @@ def main():
         pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True, device=sample_device)
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
-        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k)
+        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling)
 
     begin = time.time()
     print("Generation Start!!!")

@@ -42,6 +42,7 @@
 #include "mesh_normals.hpp"
 #include "mesh_score.hpp"
 #include "pc_normals.hpp"
+#include "pc_fps.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -966,6 +967,27 @@ int ma_op_pc_normals(const float* ref, int N, int ref_ld, const int32_t* nbr_idx
         if (!pc_knn_shape_ok(N, Q, k, 0)) throw MaError(MA_ERR_INVALID, "ma_op_pc_normals: need 3 <= k <= 32, k <= N <= 2^22 and 1 <= Q <= 2^20");
         if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_normals: ref_ld must be 3 or 6");
         HIP_CHECK(pcn::launch_normals(ref, N, ref_ld, nbr_idx, Q, k, normals, eigvals, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- farthest-point sampling of a point cloud (csrc/pc_fps.hpp) ------------------------------------------------------------------
+static_assert(MA_PC_FPS_MAX_POINTS == fps::MAX_POINTS && MA_PC_FPS_ONE_MAX_POINTS == fps::ONE_MAX_POINTS, "the header's limits are the kernels'");
+static bool pc_fps_shape_ok(int N, int n, int form) {
+    return n >= 1 && n <= N && N <= MA_PC_FPS_MAX_POINTS && n <= MA_PC_FPS_MAX_PICKS && form >= 0 && form <= 2;
+}
+
+size_t ma_pc_fps_workspace_bytes(int N, int n, int form) { return pc_fps_shape_ok(N, n, form) ? fps::layout(N).bytes : 0; }
+
+int ma_op_pc_fps(const float* ref, int N, int ref_ld, int n, int start, int form, int32_t* idx, float* d2, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !idx || !d2 || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: null pointer");
+        if (!pc_fps_shape_ok(N, n, form)) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: need 1 <= n <= N <= 2^22, n <= 2^16 and form in 0..2");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: ref_ld must be 3 or 6");
+        if (start < -1 || start >= N) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: start must be -1 or a row in [0, N)");
+        if (form == 1 && N > fps::ONE_MAX_POINTS)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: form 1 (one workgroup) holds at most MA_PC_FPS_ONE_MAX_POINTS = 16384 points");
+        if (ws_bytes < fps::layout(N).bytes) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: workspace smaller than ma_pc_fps_workspace_bytes(N, n, form)");
+        HIP_CHECK(fps::launch_fps(ref, N, ref_ld, n, start, fps::resolve_form(N, form), idx, d2, workspace, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

@@ -36,15 +36,29 @@ class Dataset:
     n_points.  The same n_points rows as the pc_normal branch would draw are kept and their normals estimated from normal_k
     neighbours on the GPU (pc_normals.xyz_to_pc_normal).  It is not called 'pc': that is the reference's command-line default, a type
     its Dataset does not know and which therefore yields an empty dataset; that behaviour is restated here and pinned by the tests,
-    so the new type needs a name of its own."""
+    so the new type needs a name of its own.
 
-    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16):
+    point_sampling="fps" (pc_normal and pc_xyz; the reference has nothing like it): the n_points rows are the ones farthest-point
+    sampling keeps (pc_fps.farthest_point_sample on the GPU over the first three columns as float32, N <= 2^22, finite), in pick
+    order, instead of a uniform draw: a scan's density follows the scanner, and a uniform draw leaves its thin parts a handful of
+    points.  Such an input consumes no draws from the numpy RNG.  With "mesh" it is a ValueError."""
+
+    def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
+                 point_sampling: str = "random"):
         self.data: List[Dict] = []
+        if point_sampling not in ("random", "fps"):
+            raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
+        if point_sampling == "fps" and input_type == "mesh":
+            raise ValueError('point_sampling="fps" applies to pc_normal and pc_xyz inputs: the points of a mesh input are already drawn from its surface')
         if input_type == "pc_normal":
             for input_path in input_list:
                 cur_data = np.load(input_path)
-                assert cur_data.shape[0] >= n_points, "input pc_normal should have at least 4096 points"
-                idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
+                if point_sampling == "fps":
+                    from .pc_fps import fps_rows
+                    idx = fps_rows(cur_data, n_points, device=sample_device or "cuda")   # shape, length, finite: checked before the GPU is touched
+                else:
+                    assert cur_data.shape[0] >= n_points, "input pc_normal should have at least 4096 points"
+                    idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
                 cur_data = cur_data[idx]
                 self.data.append({"pc_normal": cur_data, "uid": uid_of(input_path)})
         elif input_type == "mesh":
@@ -62,7 +76,7 @@ class Dataset:
             for input_path in input_list:
                 cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
                 cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
-                self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda"),
+                self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling),
                                   "uid": uid_of(input_path)})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
         print(f"dataset total data samples: {len(self.data)}")

@@ -168,21 +168,33 @@ def check_xyz(xyz, n_points: int, k: int) -> np.ndarray:
     return xyz
 
 
-def xyz_to_pc_normal(xyz, n_points: int = 4096, k: int = 16, device="cuda") -> np.ndarray:
+def xyz_to_pc_normal(xyz, n_points: int = 4096, k: int = 16, device="cuda", sampling: str = "random") -> np.ndarray:
     """xyz (N, >= 3), N >= n_points, only the first three columns are read -> (n_points, 6) in xyz's dtype: n_points rows of xyz and
     their estimated, consistently oriented unit normals.
 
     The rows are `np.random.choice(N, n_points, replace=False)` from the GLOBAL numpy RNG, the draw Dataset's pc_normal branch makes.
+    With sampling = "fps" they are the rows farthest-point sampling keeps (pc_fps.farthest_point_sample over the uploaded float32
+    cloud, automatic start), in pick order, and the global RNG is not touched.
     Each chosen point's normal comes from its k nearest neighbours in the WHOLE cloud (the dense cloud gives the better plane); the
     signs are then propagated over the k-neighbour graph of the chosen points alone (`orient_normals`)."""
     xyz = check_xyz(xyz, n_points, k)
+    if sampling not in ("random", "fps"):
+        raise ValueError(f'sampling must be "random" or "fps", got {sampling!r}')
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("xyz_to_pc_normal runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
-    idx = np.random.choice(xyz.shape[0], n_points, replace=False)
+    if sampling == "fps":
+        from .pc_fps import check_fps_args, farthest_point_sample
+        check_fps_args(xyz.shape[0], n_points, None, 0)
+    else:
+        idx = np.random.choice(xyz.shape[0], n_points, replace=False)
     with torch.cuda.device(dev):
         cloud = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], dtype=np.float32)).to(dev)
-        rows = torch.from_numpy(idx.astype(np.int32)).to(dev)
+        if sampling == "fps":
+            rows = farthest_point_sample(cloud, n_points)[0]
+            idx = rows.cpu().numpy().astype(np.int64)
+        else:
+            rows = torch.from_numpy(idx.astype(np.int32)).to(dev)
         nbr, _ = knn(cloud, rows, k)
         normals, _ = estimate_normals(cloud, nbr)
         chosen = cloud[rows.long()].contiguous()
