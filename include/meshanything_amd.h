@@ -312,6 +312,48 @@ MA_API int  ma_op_occupy_cus(int n_blocks, int lds_bytes, int64_t microseconds, 
  * IEEE half.  Per calling thread; parity tests run every 16-bit kernel in both formats.  No reference counterpart. */
 MA_API int  ma_op_set_half_dtype(int dtype);
 
+/* ---- test aids: the dense GEMM dispatcher and the LayerNorm row kernel in every form the dense phases use them in (csrc/gemm256.hpp
+ * launch_gemm_dense, csrc/gemm.hpp launch_gemm, csrc/dense_ops.hpp launch_ln_rows2 -- the launchers themselves, not a copy of their logic).  Have no
+ * reference counterpart (the reference calls nn.Linear / nn.LayerNorm on whole tensors).  Need no engine; errors via ma_last_error(NULL); every
+ * argument is checked before the first launch (MA_ERR_INVALID); all arrays are device memory, 16-byte aligned.
+ * ma_op_gemm_dense: C = act(A . W^T + bias) + R with everything a dense phase can set.
+ *   precision 0: the fp32 kernels (A, W, C fp32; impl 0 = MFMA, 1 = the plain kernel; lda % 4 == 0, K % 32 == 0; no Cb, part, split or KV planes).
+ *   precision 1: the 16-bit dispatcher in the format of ma_op_set_half_dtype (A, W, Cb 16-bit; C fp32; either output may be NULL; K % 32 == 0,
+ *     lda % 8 == 0, ldc / ldr / ldcb % 4 == 0), `variant` / `tile256` as in ma_op_gemm_bf16_tuned.
+ *   Row m of the result leaves for physical row cmap(m) = (m / grp) * gstride + m % grp + off of C / Cb (grp 0: row m); r_mod > 0: the residual row is
+ *   m % r_mod.  part 0: all rows | 1: rows [0, M - M % 256) | 2: the rows behind them (needs the identity row map and r_mod 0).
+ *   max_parts 2 .. 4: the fp32 output may come as partial sums along K in the buffers C + p * part_stride (bias and residual in part 0), see out_parts.
+ *   kv_k / kv_v (both or neither; needs N == 3 * kv_col0, kv_col0 % 64 == 0): the K | V columns [kv_col0, 3 kv_col0) of the leading out_kv_rows rows go
+ *   to plane[(m / kv_T) * kv_row_stride + ((col % kv_col0 / 64) * kv_max_seq + m % kv_T) * 64 + col % 64] instead of Cb.
+ *   Out (what the dispatcher chose): out_parts (1: not split), out_split_rows (the leading rows that are split; the rows behind them are complete in
+ *   part 0), out_kv_rows, out_rows256 (the leading rows computed on 256-row tiles).
+ * ma_op_ln_rows: nn.LayerNorm over the D columns of `rows` rows: input row r = x[xin(r) * ldx ..], output row r at physical row yout(r) of y32 (fp32,
+ *   optional, may be x itself when the two row maps and leading dimensions agree) and of `act` (optional; act_dtype 0: fp32, 1: the 16-bit format).
+ *   parts 2 | 4 (D == 1024 only): the input of rows < split_rows is the sum of `parts` buffers x + p * part_stride.
+ *   D % 4 == 0, 0 < D <= 4096, rows > 0, split_rows in [0, rows]; ma_op_layernorm refuses the same shapes. */
+typedef struct ma_gemm_dense_args {
+    int32_t struct_size;                 /* = sizeof(ma_gemm_dense_args) */
+    int32_t precision, impl;
+    int32_t M, N, K, act;
+    int32_t lda, ldr, ldc, ldcb, r_mod;
+    int32_t cmap_grp, cmap_gstride, cmap_off;
+    int32_t part;
+    int32_t max_parts;                   /* 0 | 1: never split */
+    int32_t kv_max_seq, kv_T, kv_col0;
+    int32_t variant, tile256;
+    int32_t out_parts, out_split_rows, out_kv_rows, out_rows256;
+    int64_t part_stride;                 /* floats */
+    uint64_t kv_row_stride;              /* elements */
+    const void *A, *W;
+    const float *bias, *R;
+    float *C;
+    void *Cb, *kv_k, *kv_v;
+} ma_gemm_dense_args;
+MA_API int  ma_op_gemm_dense(ma_gemm_dense_args *args, void *stream);
+MA_API int  ma_op_ln_rows(const float *x, int ldx, int xin_grp, int xin_gstride, int xin_off, const float *g, const float *b, float eps,
+                          float *y32, int ld32, void *act, int lda, int act_dtype, int yout_grp, int yout_gstride, int yout_off,
+                          int rows, int D, int parts, int64_t part_stride, int split_rows, void *stream);
+
 /* ---- measurement aid: dst[0, bytes) = src[0, bytes) as a 16-byte-per-lane streaming copy; bytes % 16 == 0; mode 0 = 2048 blocks grid-stride with
  * non-temporal accesses, 1 = one element per thread with plain accesses, 2 = one element per thread non-temporal.  bench.py times all three and
  * reports the box's achievable HBM rate next to the 8 TB/s vendor number.  No reference counterpart. */

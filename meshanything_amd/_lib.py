@@ -47,6 +47,19 @@ class KernelTiming(C.Structure):
     _fields_ = [("launches", C.c_int32 * 8), ("ms", C.c_float * 8), ("step_ms_graph", C.c_float), ("step_ms_eager", C.c_float)]
 
 
+class GemmDenseArgs(C.Structure):
+    """ma_gemm_dense_args (test aid ma_op_gemm_dense): struct_size is filled in here; the out_* fields are written by the call."""
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "precision", "impl", "M", "N", "K", "act", "lda", "ldr", "ldc", "ldcb", "r_mod", "cmap_grp",
+                                          "cmap_gstride", "cmap_off", "part", "max_parts", "kv_max_seq", "kv_T", "kv_col0", "variant", "tile256",
+                                          "out_parts", "out_split_rows", "out_kv_rows", "out_rows256")] +
+                [("part_stride", C.c_int64), ("kv_row_stride", C.c_uint64)] +
+                [(n, C.c_void_p) for n in ("A", "W", "bias", "R", "C", "Cb", "kv_k", "kv_v")])
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GemmDenseArgs)
+
+
 # every symbol include/meshanything_amd.h declares: name -> (restype, argtypes)
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -96,6 +109,8 @@ SIGNATURES = {
     "ma_op_occupy_cus": (_I, [_I, _I, C.c_int64, _P, _P]),
     "ma_op_stream_copy": (_I, [_P, _P, C.c_size_t, _I, _P]),
     "ma_op_set_half_dtype": (_I, [_I]),
+    "ma_op_gemm_dense": (_I, [C.POINTER(GemmDenseArgs), _P]),
+    "ma_op_ln_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_int64, _I, _P]),
     "ma_engine_persist_available": (_I, [_P]),
     "ma_persist_trace": (_I, [_P, _I, _P, C.POINTER(C.c_int32), _P]),
     "ma_engine_read_logits": (_I, [_P, _I, _P, _P]),

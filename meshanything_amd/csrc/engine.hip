@@ -447,11 +447,115 @@ int ma_op_gemm_bf16_tuned(const void* A, int lda, const void* W, const float* bi
     });
 }
 
+namespace {
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+void check_row_map(const std::string& op, const char* what, int grp, int gstride, int off) {
+    if (grp < 0 || off < 0 || (grp > 0 && gstride < grp)) throw MaError(MA_ERR_INVALID, op + ": " + what + " row map needs grp >= 0, off >= 0 and gstride >= grp");
+}
+// what ln_rows2_kernel can compute: a lane holds at most 16 float4 chunks of a row, the split input exists for 1024 columns only
+void check_ln_shape(const std::string& op, int rows, int D, int parts, int64_t part_stride, int split_rows) {
+    if (rows <= 0 || D <= 0) throw MaError(MA_ERR_INVALID, op + ": rows and D must be > 0");
+    if (D % 4 != 0 || D > 4096) throw MaError(MA_ERR_INVALID, op + ": D must be a multiple of 4 and at most 4096");
+    if (parts != 1 && parts != 2 && parts != 4) throw MaError(MA_ERR_INVALID, op + ": parts must be 1, 2 or 4");
+    if (parts > 1 && D != 1024) throw MaError(MA_ERR_INVALID, op + ": a split input needs D == 1024");
+    if (parts > 1 && (part_stride <= 0 || part_stride % 4 != 0)) throw MaError(MA_ERR_INVALID, op + ": part_stride must be a positive multiple of 4");
+    if (split_rows < 0 || split_rows > rows) throw MaError(MA_ERR_INVALID, op + ": split_rows outside [0, rows]");
+}
+}  // namespace
+
 int ma_op_layernorm(const float* x, int ldx, const float* g, const float* b, float eps, float* y, int ldy, int rows, int D, void* stream) {
     return guarded(nullptr, [&] {
         if (!x || !g || !b || !y) throw MaError(MA_ERR_INVALID, "ma_op_layernorm: null pointer");
+        check_ln_shape("ma_op_layernorm", rows, D, 1, 0, 0);
+        if (ldx < D || ldy < D || ldx % 4 || ldy % 4) throw MaError(MA_ERR_INVALID, "ma_op_layernorm: leading dimensions must be multiples of 4 and at least D");
         launch_ln_rows2<float>(x, ldx, RowMap{0, 0, 0}, g, b, eps, y, ldy, (float*)nullptr, 0, RowMap{0, 0, 0}, rows, D, reinterpret_cast<hipStream_t>(stream));
         HIP_CHECK(hipGetLastError());
+    });
+}
+
+// test aid: launch_ln_rows2 with everything Dense::lnrows can set
+int ma_op_ln_rows(const float* x, int ldx, int xin_grp, int xin_gstride, int xin_off, const float* g, const float* b, float eps, float* y32, int ld32, void* act,
+                  int lda, int act_dtype, int yout_grp, int yout_gstride, int yout_off, int rows, int D, int parts, int64_t part_stride, int split_rows, void* stream) {
+    return guarded(nullptr, [&] {
+        const std::string op = "ma_op_ln_rows";
+        if (!x || !g || !b || (!y32 && !act)) throw MaError(MA_ERR_INVALID, op + ": null pointer");
+        check_ln_shape(op, rows, D, parts, part_stride, split_rows);
+        if (act_dtype != 0 && act_dtype != 1) throw MaError(MA_ERR_INVALID, op + ": act_dtype must be 0 (fp32) or 1 (the 16-bit format)");
+        if (ldx < D || ldx % 4 || (y32 && (ld32 < D || ld32 % 4)) || (act && (lda < D || lda % 4)))
+            throw MaError(MA_ERR_INVALID, op + ": leading dimensions must be multiples of 4 and at least D");
+        if (!aligned16(x) || !aligned16(g) || !aligned16(b) || !aligned16(y32) || !aligned16(act)) throw MaError(MA_ERR_INVALID, op + ": arrays must be 16-byte aligned");
+        check_row_map(op, "input", xin_grp, xin_gstride, xin_off);
+        check_row_map(op, "output", yout_grp, yout_gstride, yout_off);
+        const RowMap xin{xin_grp, xin_gstride, xin_off}, yout{yout_grp, yout_gstride, yout_off};
+        // (a wave reads its whole row before it writes: in place is safe exactly when a row is written where it was read)
+        if (y32 == x && (ld32 != ldx || xin_grp != yout_grp || (xin_grp > 0 && xin_gstride != yout_gstride) || xin_off != yout_off))
+            throw MaError(MA_ERR_INVALID, op + ": y32 over x needs the same leading dimension and row map on both sides");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        if (act_dtype == 1) H16_DO(g_op_hdt, HT, launch_ln_rows2<HT>(x, ldx, xin, g, b, eps, y32, ld32, reinterpret_cast<HT*>(act), lda, yout, rows, D, s, parts, (long)part_stride, split_rows));
+        else launch_ln_rows2<float>(x, ldx, xin, g, b, eps, y32, ld32, reinterpret_cast<float*>(act), lda, yout, rows, D, s, parts, (long)part_stride, split_rows);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// test aid: launch_gemm_dense / launch_gemm with everything Dense::gemm can set; reports what the dispatcher chose
+int ma_op_gemm_dense(ma_gemm_dense_args* a, void* stream) {
+    return guarded(nullptr, [&] {
+        const std::string op = "ma_op_gemm_dense";
+        if (!a) throw MaError(MA_ERR_INVALID, op + ": null arguments");
+        if (a->struct_size != (int32_t)sizeof(ma_gemm_dense_args)) throw MaError(MA_ERR_INVALID, op + ": struct_size mismatch");
+        a->out_parts = 1; a->out_split_rows = 0; a->out_kv_rows = 0; a->out_rows256 = 0;
+        auto bad = [&](const char* what) { throw MaError(MA_ERR_INVALID, op + ": " + what); };
+        if (a->precision != 0 && a->precision != 1) bad("precision must be 0 (fp32 kernels) or 1 (16-bit dispatcher)");
+        const bool is16 = a->precision == 1;
+        if (!a->A || !a->W || (!a->C && !a->Cb)) bad("null pointer");
+        if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->K % 32 != 0) bad("need M, N > 0 and K a positive multiple of 32");
+        if (a->act != MA_ACT_NONE && a->act != MA_ACT_RELU && a->act != MA_ACT_GELU) bad("act must be 0, 1 or 2");
+        if (a->lda < a->K || a->lda % (is16 ? 8 : 4)) bad("lda must be at least K and a multiple of 8 (16-bit) / 4 (fp32)");
+        if (a->C && (a->ldc < a->N || a->ldc % 4)) bad("ldc must be at least N and a multiple of 4");
+        if (a->R && (a->ldr < a->N || a->ldr % 4)) bad("ldr must be at least N and a multiple of 4");
+        if (a->Cb && (a->ldcb < a->N || a->ldcb % 4)) bad("ldcb must be at least N and a multiple of 4");
+        if (!aligned16(a->A) || !aligned16(a->W) || !aligned16(a->bias) || !aligned16(a->R) || !aligned16(a->C) || !aligned16(a->Cb) || !aligned16(a->kv_k) || !aligned16(a->kv_v))
+            bad("arrays must be 16-byte aligned");
+        check_row_map(op, "output", a->cmap_grp, a->cmap_gstride, a->cmap_off);
+        if (a->r_mod < 0) bad("r_mod must be >= 0");
+        if (a->part < 0 || a->part > 2) bad("part must be 0, 1 or 2");
+        if (a->part != 0 && (a->cmap_grp != 0 || a->r_mod != 0)) bad("a GEMM by row parts takes no row map and no broadcast residual");
+        if (a->max_parts < 0 || a->max_parts > 4) bad("max_parts must be in [0, 4]");
+        if (a->max_parts >= 2 && (!a->C || a->part_stride <= 0 || a->part_stride % 4 != 0)) bad("a split along K needs the fp32 output and part_stride a positive multiple of 4");
+        const bool kv = a->kv_k || a->kv_v;
+        if (kv) {
+            if (!a->kv_k || !a->kv_v) bad("kv_k and kv_v come together");
+            if (a->kv_col0 < 64 || a->kv_col0 % 64 != 0 || a->N != 3 * a->kv_col0) bad("the KV planes need kv_col0 a multiple of 64 and N == 3 * kv_col0");
+            if (a->kv_T < 1 || a->kv_max_seq < a->kv_T) bad("the KV planes need 1 <= kv_T <= kv_max_seq");
+            if (a->kv_row_stride % 8 != 0 || a->kv_row_stride < (uint64_t)(a->kv_col0 / 64) * (uint64_t)a->kv_max_seq * 64u) bad("kv_row_stride must hold a sample's (heads, kv_max_seq, 64) plane and be a multiple of 8");
+            if (!a->Cb) bad("the KV planes need the 16-bit output");
+        }
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        if (!is16) {
+            if (a->Cb || a->part != 0 || a->max_parts >= 2 || kv) bad("precision 0 has the fp32 output only: no Cb, part, split along K or KV planes");
+            if (a->impl != 0 && a->impl != 1) bad("impl must be 0 (MFMA) or 1 (plain)");
+            GemmArgs g{};
+            g.A = reinterpret_cast<const float*>(a->A); g.lda = a->lda; g.W = a->W; g.bias = a->bias; g.R = a->R; g.ldr = a->ldr; g.C = a->C; g.ldc = a->ldc;
+            g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act; g.r_mod = a->r_mod; g.cmap = RowMap{a->cmap_grp, a->cmap_gstride, a->cmap_off};
+            op_launched(launch_gemm<float>(g, a->impl, s), "ma_op_gemm_dense");
+            return;
+        }
+        check_value(find_option("gemm_variant", true), a->variant);
+        check_value(find_option("gemm256", true), a->tile256);
+        GemmTune tune{};
+        tune.variant = a->variant; tune.tile256 = a->tile256;
+        GemmTArgs t{};
+        t.A = reinterpret_cast<const bf16_t*>(a->A); t.lda = a->lda; t.W = reinterpret_cast<const bf16_t*>(a->W); t.bias = a->bias; t.R = a->R; t.ldr = a->ldr;
+        t.C = a->C; t.ldc = a->ldc; t.Cb = reinterpret_cast<bf16_t*>(a->Cb); t.ldcb = a->ldcb; t.M = a->M; t.N = a->N; t.K = a->K; t.act = a->act;
+        t.r_mod = a->r_mod; t.cmap = RowMap{a->cmap_grp, a->cmap_gstride, a->cmap_off}; t.xcd_swizzle = 1; t.part = a->part;
+        if (kv) { t.kv_k = reinterpret_cast<bf16_t*>(a->kv_k); t.kv_v = reinterpret_cast<bf16_t*>(a->kv_v); t.kv_row_stride = (size_t)a->kv_row_stride; t.kv_max_seq = a->kv_max_seq; t.kv_T = a->kv_T; t.kv_col0 = a->kv_col0; }
+        GemmSplitK sk;
+        sk.max_parts = std::max(1, (int)a->max_parts); sk.part_stride = (long)a->part_stride;
+        static int n_cus = -1;
+        if (n_cus < 0) { int dev = 0; hipDeviceProp_t prop; n_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0; }
+        int kv_rows = 0, rows256 = 0;
+        op_launched(H16_CALL(g_op_hdt, HT, launch_gemm_dense<HT>(t, n_cus, s, kv ? &kv_rows : nullptr, &sk, nullptr, tune, &rows256)), "ma_op_gemm_dense");
+        a->out_parts = sk.parts; a->out_split_rows = sk.rows; a->out_kv_rows = kv_rows; a->out_rows256 = rows256;
     });
 }
 

@@ -742,20 +742,24 @@ struct GemmSplitK { int max_parts = 1; long part_stride = 0; int parts = 1; int 
 // Cb its 16-bit copy.  On return `rows` = the leading rows for which the GEMM did it (the one-tile kernel's LNF form; 0: none) -- the caller runs the
 // row kernel over the rows behind them, whose plain sums were written to `tail_c` (same leading dimension as C) instead of C.
 struct GemmLnFuse { G256Ln ln; float* tail_c = nullptr; int rows = 0; };
-template <typename HT> inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune);
+// rows256 (optional, host side only): the number of leading rows this problem computes on the 256-row tiles (0: none; with a row map the ragged last tile row
+// counts as far as M) -- what a kernel-level test asserts so that it cannot quietly test another kernel
+template <typename HT> inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune, int* rows256);
 template <typename HT>
-inline hipError_t launch_gemm_dense(const GemmTArgs& g, int n_cus, hipStream_t s, int* kv_rows = nullptr, GemmSplitK* sk = nullptr, GemmLnFuse* lnf = nullptr, const GemmTune& tune = {}) {
+inline hipError_t launch_gemm_dense(const GemmTArgs& g, int n_cus, hipStream_t s, int* kv_rows = nullptr, GemmSplitK* sk = nullptr, GemmLnFuse* lnf = nullptr, const GemmTune& tune = {},
+                                    int* rows256 = nullptr) {
+    if (rows256) *rows256 = 0;
     if (lnf && lnf->tail_c) {
         // every launch that does NOT finish the LayerNorm writes plain sums to the caller's tail buffer and no 16-bit copy (the caller's row kernel follows)
         GemmTArgs plain = g;
         plain.C = lnf->tail_c; plain.Cb = nullptr;
-        return launch_gemm_dense_impl<HT>(plain, g, n_cus, s, kv_rows, sk, lnf, tune);
+        return launch_gemm_dense_impl<HT>(plain, g, n_cus, s, kv_rows, sk, lnf, tune, rows256);
     }
-    return launch_gemm_dense_impl<HT>(g, g, n_cus, s, kv_rows, sk, nullptr, tune);
+    return launch_gemm_dense_impl<HT>(g, g, n_cus, s, kv_rows, sk, nullptr, tune, rows256);
 }
 // g: the arguments of the plain launches; g_ln: those of the LNF launch (outputs = the LayerNorm's)
 template <typename HT>
-inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune) {
+inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_ln, int n_cus, hipStream_t s, int* kv_rows, GemmSplitK* sk, GemmLnFuse* lnf, const GemmTune& tune, int* rows256) {
     if (kv_rows) *kv_rows = 0;
     if (sk) { sk->parts = 1; sk->rows = 0; }
     if (lnf) lnf->rows = 0;
@@ -822,6 +826,7 @@ inline hipError_t launch_gemm_dense_impl(const GemmTArgs& g, const GemmTArgs& g_
         if (nty > 0) {
             GemmTArgs m = g;
             m.M = can_split ? nty * 256 : g.M;
+            if (rows256) *rows256 = m.M;
             // whole tiles with 16-bit output: the persistent form (next tile's operands requested before this tile's epilogue; its 4-KB-patch epilogue is
             // the faster one even where every workgroup has a single tile)
             const bool persist = tune.tile256 >= 2 && can_split && !g.C && g.Cb && !g.R && g.N % 256 == 0 && n_cus >= 8;
