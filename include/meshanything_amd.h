@@ -547,6 +547,35 @@ MA_API int    ma_op_pc_fps(const float *ref, int N, int ref_ld, int n, int start
                            size_t ws_bytes, void *stream);
 MA_API size_t ma_pc_fps_workspace_bytes(int N, int n, int form);
 
+/* ---- neighbours of EVERY point over a uniform cell grid, for statistical outlier removal, --outlier_k (csrc/pc_grid.hpp).  Has no
+ * reference counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device
+ * arrays (origin and dims are HOST arrays of 3), caller-owned workspace, asynchronous on `stream`.
+ *
+ * ma_op_pc_knn_grid: every row of ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6, is a query.  The key of row r for a
+ *   query at (qx, qy, qz) is ma_op_pc_knn's, exactly
+ *       d = fl32(fl32(dx * dx + dy * dy) + dz * dz),  dx = fl32(qx - rx), dy = fl32(qy - ry), dz = fl32(qz - rz)
+ *   (no FMA contraction; a NaN key counts as +inf), and neighbours are ordered by the pair (d, r) ascending, a total order.  The k best
+ *   under a total order are unique: the result does not depend on the grid, bit for bit, and nbr_idx (N, k) int32 / nbr_d2 (N, k) fp32,
+ *   in the original row order, EQUAL what ma_op_pc_knn(ref, N, ref_ld, NULL, N, k, ...) writes.  mean_dist (N) float64 =
+ *   (sum_j sqrt((double) d_j)) / k, summed in list order without contraction; the list includes the point itself at distance 0.  Each
+ *   of the three outputs may be NULL, at least one must be given; with mean_dist alone the lists are never written to memory.
+ *   The grid only decides the time.  origin[3] finite, cell finite and > 0, dims[3] each in 1 .. MA_PC_GRID_MAX_DIM with a product of
+ *   at most MA_PC_GRID_MAX_CELLS.  Per axis face[i] = fl32(origin + fl32(i * cell)), i = 0 .. dim, and the cell of a coordinate x is
+ *   the largest i in [0, dim - 1] with i = 0 or face[i] <= x, by comparisons alone: the border cells are unbounded outward, a point
+ *   outside the box belongs to the nearest border cell (fit the box to the object, not to its strays), a NaN goes to cell 0.  A
+ *   query's block of cells grows ring by ring from its own cell until it is the whole grid or the list is full with its k-th key
+ *   strictly below fl32(b * b) for the distance b = fl32(q - face) to every side of the block that is not a grid border.  The order of
+ *   the points inside a cell comes from atomics and differs between runs; no output depends on it.  Non-finite coordinates: unspecified
+ *   neighbours, nothing read or written out of bounds.
+ *   MA_PC_KNN_MIN_K <= k <= MA_PC_KNN_MAX_K, k <= N <= MA_PC_GRID_MAX_POINTS.  workspace: ma_pc_knn_grid_workspace_bytes(N, k, nx, ny, nz)
+ *   bytes of device memory (0 for arguments outside those limits); its contents on entry do not matter. */
+#define MA_PC_GRID_MAX_POINTS (1 << 22)
+#define MA_PC_GRID_MAX_DIM 128
+#define MA_PC_GRID_MAX_CELLS (1 << 21)
+MA_API int    ma_op_pc_knn_grid(const float *ref, int N, int ref_ld, int k, const float *origin, float cell, const int32_t *dims, int32_t *nbr_idx,
+                                float *nbr_d2, double *mean_dist, void *workspace, size_t ws_bytes, void *stream);
+MA_API size_t ma_pc_knn_grid_workspace_bytes(int N, int k, int nx, int ny, int nz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,10 @@ shape (N, >= 3), .xyz or .txt) and estimates them on the GPU from `--normal_k` n
 `--point_sampling fps` (with pc_normal and pc_xyz) keeps the 4096 points farthest-point sampling picks on the GPU
 (`meshanything_amd/pc_fps.py`) instead of the reference's uniform draw; such an input consumes no draws from the numpy RNG, so the RNG
 state later stages see differs from a `--point_sampling random` run.
+`--outlier_k K` (with pc_normal and pc_xyz; 0 = off, the default) removes statistical outliers first: the rows whose mean distance to
+their K nearest neighbours exceeds the cloud's mean by more than `--outlier_std` standard deviations, found on the GPU over a cell grid
+(`meshanything_amd/pc_outliers.py`); sampling and normal estimation then see the survivors only, and one line per input reports how many
+rows went.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -61,7 +65,17 @@ def get_args(argv=None):
                    help="winding of the written faces: by signed volume (fix_normals, the reference) or by the cloud's normals")
     p.add_argument("--point_sampling", default="random", choices=["random", "fps"],
                    help="with --input_type pc_normal / pc_xyz: which 4096 rows of the input to keep: a uniform draw (the reference) or farthest-point sampling on the GPU")
+    p.add_argument("--outlier_k", default=0, type=int,
+                   help="with --input_type pc_normal / pc_xyz: remove statistical outliers first, from this many neighbours per point (3..32; 0 = off)")
+    p.add_argument("--outlier_std", default=2.0, type=float,
+                   help="with --outlier_k: drop a point whose mean neighbour distance exceeds the cloud's mean by more than this many standard deviations")
     args = p.parse_args(argv)
+    if args.outlier_k != 0 and not 3 <= args.outlier_k <= 32:
+        p.error("--outlier_k must be 0 (off) or in 3..32")
+    if not (0.0 <= args.outlier_std < float("inf")):
+        p.error("--outlier_std must be finite and >= 0")
+    if args.outlier_k != 0 and args.input_type == "mesh":
+        p.error("--outlier_k applies to --input_type pc_normal and pc_xyz, not to mesh inputs")
     if args.point_sampling == "fps" and args.input_type == "mesh":
         p.error("--point_sampling fps applies to --input_type pc_normal and pc_xyz, not to mesh inputs")
     if not 3 <= args.normal_k <= 32:
@@ -122,7 +136,8 @@ def main():
         pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True, device=sample_device)
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
-        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling)
+        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling,
+                          outlier_k=args.outlier_k, outlier_std=args.outlier_std)
 
     begin = time.time()
     print("Generation Start!!!")

@@ -134,6 +134,8 @@ SIGNATURES = {
     "ma_op_pc_normals": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
     "ma_op_pc_fps": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_fps_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "ma_op_pc_knn_grid": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ma_pc_knn_grid_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
 }
 
 _lib = None

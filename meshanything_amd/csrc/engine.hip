@@ -43,6 +43,7 @@
 #include "mesh_score.hpp"
 #include "pc_normals.hpp"
 #include "pc_fps.hpp"
+#include "pc_grid.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1092,6 +1093,34 @@ int ma_op_pc_fps(const float* ref, int N, int ref_ld, int n, int start, int form
             throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: form 1 (one workgroup) holds at most MA_PC_FPS_ONE_MAX_POINTS = 16384 points");
         if (ws_bytes < fps::layout(N).bytes) throw MaError(MA_ERR_INVALID, "ma_op_pc_fps: workspace smaller than ma_pc_fps_workspace_bytes(N, n, form)");
         HIP_CHECK(fps::launch_fps(ref, N, ref_ld, n, start, fps::resolve_form(N, form), idx, d2, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- neighbours of every point over a cell grid, for statistical outlier removal (csrc/pc_grid.hpp) -------------------------------------
+static_assert(MA_PC_GRID_MAX_POINTS == pcg::MAX_POINTS && MA_PC_GRID_MAX_DIM == pcg::MAX_DIM && MA_PC_GRID_MAX_CELLS == pcg::MAX_CELLS,
+              "the header's limits are the kernels'");
+static bool pc_grid_shape_ok(int N, int k, int nx, int ny, int nz) {
+    return k >= MA_PC_KNN_MIN_K && k <= MA_PC_KNN_MAX_K && N >= k && N <= MA_PC_GRID_MAX_POINTS && nx >= 1 && nx <= MA_PC_GRID_MAX_DIM && ny >= 1 &&
+           ny <= MA_PC_GRID_MAX_DIM && nz >= 1 && nz <= MA_PC_GRID_MAX_DIM && (int64_t)nx * ny * nz <= MA_PC_GRID_MAX_CELLS;
+}
+
+size_t ma_pc_knn_grid_workspace_bytes(int N, int k, int nx, int ny, int nz) { return pc_grid_shape_ok(N, k, nx, ny, nz) ? pcg::layout(N, nx * ny * nz).bytes : 0; }
+
+int ma_op_pc_knn_grid(const float* ref, int N, int ref_ld, int k, const float* origin, float cell, const int32_t* dims, int32_t* nbr_idx, float* nbr_d2,
+                      double* mean_dist, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !origin || !dims || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: null pointer");
+        if (!nbr_idx && !nbr_d2 && !mean_dist) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: no output: give at least one of nbr_idx, nbr_d2 and mean_dist");
+        if (!pc_grid_shape_ok(N, k, dims[0], dims[1], dims[2]))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: need 3 <= k <= 32, k <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: ref_ld must be 3 or 6");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: origin must be finite");
+        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: cell must be finite and > 0");
+        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
+        if (ws_bytes < pcg::layout(N, pcg::cells_of(g)).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: workspace smaller than ma_pc_knn_grid_workspace_bytes(N, k, nx, ny, nz)");
+        HIP_CHECK(pcg::launch_build(ref, N, ref_ld, g, workspace, reinterpret_cast<hipStream_t>(stream)));
+        HIP_CHECK(pcg::launch_search(N, k, g, nbr_idx, nbr_d2, mean_dist, workspace, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

@@ -7,7 +7,8 @@
 // and neighbours are ordered by the pair (d, r) ascending -- a total order, so the result is one fixed list whatever the launch shape:
 // a query is its own neighbour at distance 0, duplicates are ordinary points.
 //
-// Search: grid (tiles of 256 queries, splits).  One query per thread, its k-best list in registers (K = 8, 16 or 32 slots, the smallest
+// Search: grid (tiles of 256 queries, splits).  One query per thread, its k-best list in registers (knn_list.hpp, shared with the cell-grid
+// search of pc_grid.hpp: K = 8, 16 or 32 slots, the smallest
 // that holds k; every index is a compile-time constant, so nothing goes to scratch); the split's range of ref passes through LDS in
 // tiles of 1024 points, x / y / z apart, read four points at a time as broadcasts.  With one split the lists go straight to the output;
 // otherwise every split leaves its K-list in the workspace, [split][slot][query] so that stores and loads coalesce, and the merge
@@ -25,6 +26,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "knn_list.hpp"
 #include "watertight.hpp"
 
 namespace ma {
@@ -35,10 +37,7 @@ constexpr int REF_TILE = 1024;       // reference points staged per pass: 12 KB 
 constexpr int MIN_CHUNK = 256;       // the automatic choice gives a split at least this many reference points ...
 constexpr int TARGET_GROUPS = 1024;  // ... and stops splitting at 4 workgroups per CU of a 256-CU part
 constexpr int MAX_SPLITS = 64;
-constexpr int MAX_K = 32;
 static_assert(REF_TILE % Q_THREADS == 0 && REF_TILE % 4 == 0, "the staging loop and the float4 reads");
-
-inline int slots_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
 
 // splits == 0: enough splits to fill the chip, none shorter than MIN_CHUNK points.  A function of (N, Q) alone, so that the workspace
 // size can be asked for without a device.
@@ -53,24 +52,6 @@ inline int resolve_splits(int N, int Q, int splits) {
 inline size_t knn_ws_bytes(int N, int Q, int k, int splits) {
     const int s = resolve_splits(N, Q, splits);
     return s == 1 ? 256 : 2 * wt::align256((size_t)s * slots_for(k) * Q * sizeof(float));
-}
-
-// (d, i) before (bd, bi) in the order of the lists
-__device__ inline bool before(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
-
-// put (d, i) into the ascending list; the entry that falls off the end is dropped
-template <int K>
-__device__ inline void insert(float (&bd)[K], int (&bi)[K], float d, int i) {
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-        const bool lt = before(d, i, bd[s], bi[s]);
-        const float td = bd[s];
-        const int ti = bi[s];
-        bd[s] = lt ? d : td;
-        bi[s] = lt ? i : ti;
-        d = lt ? td : d;
-        i = lt ? ti : i;
-    }
 }
 
 template <int K>

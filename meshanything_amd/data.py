@@ -41,18 +41,32 @@ class Dataset:
     point_sampling="fps" (pc_normal and pc_xyz; the reference has nothing like it): the n_points rows are the ones farthest-point
     sampling keeps (pc_fps.farthest_point_sample on the GPU over the first three columns as float32, N <= 2^22, finite), in pick
     order, instead of a uniform draw: a scan's density follows the scanner, and a uniform draw leaves its thin parts a handful of
-    points.  Such an input consumes no draws from the numpy RNG.  With "mesh" it is a ValueError."""
+    points.  Such an input consumes no draws from the numpy RNG.  With "mesh" it is a ValueError.
+
+    outlier_k=K > 0 (pc_normal and pc_xyz; the reference has nothing like it): statistical outlier removal before anything else
+    happens (pc_outliers.remove_statistical_outliers on the GPU, K neighbours, N <= 2^22, finite): the rows whose mean distance to
+    their K nearest neighbours exceeds the cloud's mean by more than outlier_std standard deviations are dropped, the survivors keep
+    their order and stand in for the file's rows: the uniform draw or FPS runs over them, and pc_xyz takes its normals from their
+    neighbours.  One stray row would otherwise set the scale of `normalize_pc`, and FPS picks strays first.  Fewer than n_points
+    survivors is a ValueError.  0 = off: no code path and no RNG draw changes.  With "mesh" a non-zero value is a ValueError."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
-                 point_sampling: str = "random"):
+                 point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0):
         self.data: List[Dict] = []
         if point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
         if point_sampling == "fps" and input_type == "mesh":
             raise ValueError('point_sampling="fps" applies to pc_normal and pc_xyz inputs: the points of a mesh input are already drawn from its surface')
+        if outlier_k:
+            from .pc_outliers import check_filter_args, filter_rows
+            if input_type == "mesh":
+                raise ValueError("outlier_k applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
+            check_filter_args(outlier_k, outlier_std)                # before any file is read
         if input_type == "pc_normal":
             for input_path in input_list:
                 cur_data = np.load(input_path)
+                if outlier_k:
+                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
                 if point_sampling == "fps":
                     from .pc_fps import fps_rows
                     idx = fps_rows(cur_data, n_points, device=sample_device or "cuda")   # shape, length, finite: checked before the GPU is touched
@@ -76,6 +90,8 @@ class Dataset:
             for input_path in input_list:
                 cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
                 cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
+                if outlier_k:
+                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
                 self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling),
                                   "uid": uid_of(input_path)})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
