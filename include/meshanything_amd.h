@@ -576,6 +576,42 @@ MA_API int    ma_op_pc_knn_grid(const float *ref, int N, int ref_ld, int k, cons
                                 float *nbr_d2, double *mean_dist, void *workspace, size_t ws_bytes, void *stream);
 MA_API size_t ma_pc_knn_grid_workspace_bytes(int N, int k, int nx, int ny, int nz);
 
+/* ---- Euclidean clustering: the connected parts of a cloud, for --cluster_radius (csrc/pc_cluster.hpp).  Has no reference counterpart.
+ * Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays (origin, dims and
+ * pairs_bound are HOST pointers), caller-owned workspace.  NOT asynchronous: the call reads the pair bound back on `stream` before it
+ * launches the search, as ma_op_marching_cubes reads its counts.
+ *
+ * ma_op_pc_cluster: rows i and j of ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6, are LINKED iff
+ *       d(i, j) = fl32(fl32(dx * dx + dy * dy) + dz * dz) <= r2,  dx = fl32(x_i - x_j), dy = fl32(y_i - y_j), dz = fl32(z_i - z_j)
+ *   (the key of ma_op_pc_knn, no FMA contraction; a NaN key links nothing) with r2 = fl32(radius * radius), computed once on the host.
+ *   The key is symmetric (fl32(a - b) = -fl32(b - a)), equality is included, exact duplicates are always linked.  labels (N) int32:
+ *   labels[i] = the smallest row index in the connected component of i under those links.  A function of the cloud and the radius
+ *   alone: it does not depend on the grid, on the order the atomics resolve in, or on the run, so a numpy restatement gives EQUAL
+ *   labels.  sizes (N) int32, or NULL: sizes[l] = the number of rows with label l where labels[l] == l, 0 elsewhere.
+ *   The grid (origin, cell, dims: as for ma_op_pc_knn_grid, the same faces and cell rule) only decides the time.  A query's block of
+ *   cells grows ring by ring from its own cell until it is the whole grid or fl32(b * b) > r2 for the distance b = fl32(q - face) to
+ *   every side of the block that is not a grid border; every point outside the block then has a key above r2.  The components come
+ *   from a lock-free union-find whose every access is an agent-scope atomic; no thread waits for another.
+ *   The pair bound, a guard against a radius the size of the cloud (an N^2 job): before the search, sum over the cells c of n_c * (the
+ *   points in the block of R = floor(radius / cell) + 2 rings around c, clipped to the grid), 64 bits, an upper bound of the keys the
+ *   search evaluates.  It is written to *pairs_bound (if given) and, if it exceeds max_pairs (0 = MA_PC_CLUSTER_MAX_PAIRS), the call
+ *   fails with MA_ERR_INVALID, the message giving both numbers, and launches nothing further.  So that the bound holds whatever the
+ *   rounding of the faces, a grid whose float32 faces R + 1 cells apart are not more than the radius apart (an origin huge against
+ *   the cell) is refused with MA_ERR_INVALID before any device work.
+ *   MA_PC_CLUSTER_MAX_PAIRS is a guard value, not a tuning knob: 2^36.  Measured on an MI355X: a uniform cloud of
+ *   2^22 points at the radius whose bound is 6.7e10, just under it, takes 42 ms as a whole, far inside the 2 s the value was to be lowered
+ *   for, so it was not lowered.
+ *   Non-finite coordinates: such a row links nothing and is its own component; nothing is read or written out of bounds.
+ *   1 <= N <= MA_PC_GRID_MAX_POINTS, radius finite and > 0, the grid limits of ma_op_pc_knn_grid, radius / cell <= 8.  workspace:
+ *   ma_pc_cluster_workspace_bytes(N, nx, ny, nz) bytes of device memory (0 for arguments outside those limits): the grid's layout, the
+ *   parent array and the 8-byte total; its contents on entry do not matter. */
+#define MA_PC_CLUSTER_MAX_PAIRS  (1ull << 36)
+MA_API int    ma_op_pc_cluster(const float *ref, int N, int ref_ld, float radius, const float *origin, float cell, const int32_t *dims,
+                               uint64_t max_pairs /* 0 = MA_PC_CLUSTER_MAX_PAIRS */, int32_t *labels, int32_t *sizes /* or NULL */,
+                               uint64_t *pairs_bound /* host pointer or NULL: the bound that was computed */,
+                               void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,13 @@ state later stages see differs from a `--point_sampling random` run.
 their K nearest neighbours exceeds the cloud's mean by more than `--outlier_std` standard deviations, found on the GPU over a cell grid
 (`meshanything_amd/pc_outliers.py`); sampling and normal estimation then see the survivors only, and one line per input reports how many
 rows went.
+`--cluster_radius R` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) then splits what is left into the
+connected parts of the graph that links two points at most R apart, on the GPU over the same cell grid (`meshanything_amd/pc_cluster.py`),
+and drops the parts of fewer than `--cluster_min_points` points (default and least 4096): a floating clump the outlier filter cannot see,
+or a second object; one line per input reports the parts.  `--cluster_mode largest` (the default) meshes the largest part as the input;
+`--cluster_mode split` meshes every kept part as a row of the batch, writes `{uid}_part{j}_gen.obj` in the INPUT's coordinates (centre +
+scale * 2 * v, the inverse of the normalisation) and, after a file's last part, `{uid}_gen.obj`: the parts one after the other, no vertex
+merged across them.  The parts of one file stay on one rank (`dp.shard_grouped`).
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -69,7 +76,24 @@ def get_args(argv=None):
                    help="with --input_type pc_normal / pc_xyz: remove statistical outliers first, from this many neighbours per point (3..32; 0 = off)")
     p.add_argument("--outlier_std", default=2.0, type=float,
                    help="with --outlier_k: drop a point whose mean neighbour distance exceeds the cloud's mean by more than this many standard deviations")
+    p.add_argument("--cluster_radius", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: split the input into the connected parts of the graph that links points at most this "
+                        "far apart, in the units of the input file, and drop the small ones (0 = off)")
+    p.add_argument("--cluster_mode", default=None, choices=["largest", "split"],
+                   help="with --cluster_radius: mesh the largest part only (the default), or every kept part, written in the input's coordinates")
+    p.add_argument("--cluster_min_points", default=None, type=int,
+                   help="with --cluster_radius: drop the parts of fewer points than this (default 4096, the rows the encoder takes)")
     args = p.parse_args(argv)
+    if not (0.0 <= args.cluster_radius < float("inf")):
+        p.error("--cluster_radius must be finite and >= 0 (0 = off)")
+    if args.input_type == "mesh" and (args.cluster_radius != 0 or args.cluster_mode is not None or args.cluster_min_points is not None):
+        p.error("--cluster_radius, --cluster_mode and --cluster_min_points apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+    if args.cluster_radius == 0 and (args.cluster_mode is not None or args.cluster_min_points is not None):
+        p.error("--cluster_mode and --cluster_min_points need --cluster_radius > 0")
+    if args.cluster_min_points is not None and args.cluster_min_points < 4096:
+        p.error("--cluster_min_points must be at least 4096, the rows the uniform draw needs")
+    args.cluster_mode = args.cluster_mode or "largest"
+    args.cluster_min_points = 4096 if args.cluster_min_points is None else args.cluster_min_points
     if args.outlier_k != 0 and not 3 <= args.outlier_k <= 32:
         p.error("--outlier_k must be 0 (off) or in 3..32")
     if not (0.0 <= args.outlier_std < float("inf")):
@@ -95,7 +119,8 @@ def main():
     from meshanything_amd import dp
     from meshanything_amd.checkpoint import load_safetensors_items, synthetic_items
     from meshanything_amd.data import Dataset, uid_of
-    from meshanything_amd.mesh_export import faces_from_coords, fix_normals, write_obj
+    from meshanything_amd.mesh_export import faces_from_coords, fix_normals, merge_meshes, write_obj
+    from meshanything_amd.mesh_score import DEFAULT_MESH_SCALE
     from meshanything_amd.model import MeshAnything
 
     args = get_args()
@@ -137,11 +162,15 @@ def main():
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
         dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling,
-                          outlier_k=args.outlier_k, outlier_std=args.outlier_std)
+                          outlier_k=args.outlier_k, outlier_std=args.outlier_std, cluster_radius=args.cluster_radius, cluster_mode=args.cluster_mode,
+                          cluster_min_points=args.cluster_min_points)
 
     begin = time.time()
     print("Generation Start!!!")
-    mine = dp.shard_indices(len(dataset), rank, world)
+    split = args.cluster_radius > 0 and args.cluster_mode == "split"
+    groups = dataset.groups() if split else None
+    group_parts = {}                                 # --cluster_mode split: a group's parts so far, in part order (one rank holds a whole group)
+    mine = dp.shard_grouped(groups, rank, world) if split else dp.shard_indices(len(dataset), rank, world)
     for batch in dp.batches(mine, args.batchsize_per_gpu):
         data = [dataset[i] for i in batch]
         pc = torch.from_numpy(np.stack([d["pc_normal"] for d in data])).cuda()
@@ -155,13 +184,23 @@ def main():
                 print(line if nc is None else line + ", NC " + " ".join(f"{v:.6f}" for v in nc))
         else:
             outputs = model(pc, sampling=args.sampling, orient=orient).cpu().numpy()
-        for d, coords in zip(data, outputs):
+        for i, d, coords in zip(batch, data, outputs):
             verts, faces = faces_from_coords(coords)
             if orient is None:                       # --orient cloud: the winding came with the coordinates
                 faces = fix_normals(verts, faces)
+            if split:                                # into the input file's frame, in float64: the decoder's +-0.5 times 2 is the unit box
+                centre, scale = d["frame"]
+                verts = centre[None, :] + scale * DEFAULT_MESH_SCALE * verts.astype(np.float64)
             path = os.path.join(out_dir, f'{d["uid"]}_gen.obj')
             write_obj(path, verts, faces)
             print(f"{path} Over!!")
+            if split:
+                parts = group_parts.setdefault(groups[i], [])
+                parts.append((verts, faces))
+                if len(parts) == groups.count(groups[i]):            # the group's last part: the parts in one file, nothing merged across them
+                    path = os.path.join(out_dir, f'{d["group"]}_gen.obj')
+                    write_obj(path, *merge_meshes(group_parts.pop(groups[i])))
+                    print(f"{path} Over!!")
     print(f"Total time: {time.time() - begin}")
     if world > 1:
         torch.distributed.barrier()

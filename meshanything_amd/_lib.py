@@ -136,6 +136,8 @@ SIGNATURES = {
     "ma_pc_fps_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ma_op_pc_knn_grid": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_knn_grid_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "ma_op_pc_cluster": (_I, [_P, _I, _I, _F, _P, _F, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64), _P, C.c_size_t, _P]),
+    "ma_pc_cluster_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
 }
 
 _lib = None

@@ -44,6 +44,7 @@
 #include "pc_normals.hpp"
 #include "pc_fps.hpp"
 #include "pc_grid.hpp"
+#include "pc_cluster.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1121,6 +1122,48 @@ int ma_op_pc_knn_grid(const float* ref, int N, int ref_ld, int k, const float* o
             throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: workspace smaller than ma_pc_knn_grid_workspace_bytes(N, k, nx, ny, nz)");
         HIP_CHECK(pcg::launch_build(ref, N, ref_ld, g, workspace, reinterpret_cast<hipStream_t>(stream)));
         HIP_CHECK(pcg::launch_search(N, k, g, nbr_idx, nbr_d2, mean_dist, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+
+// ---- Euclidean clustering over the cell grid (csrc/pc_cluster.hpp) ------------------------------------------------------------------------
+static bool pc_cluster_shape_ok(int N, int nx, int ny, int nz) {
+    return N >= 1 && N <= MA_PC_GRID_MAX_POINTS && nx >= 1 && nx <= MA_PC_GRID_MAX_DIM && ny >= 1 && ny <= MA_PC_GRID_MAX_DIM && nz >= 1 &&
+           nz <= MA_PC_GRID_MAX_DIM && (int64_t)nx * ny * nz <= MA_PC_GRID_MAX_CELLS;
+}
+
+size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcc::layout(N, nx * ny * nz).bytes : 0; }
+
+int ma_op_pc_cluster(const float* ref, int N, int ref_ld, float radius, const float* origin, float cell, const int32_t* dims, uint64_t max_pairs,
+                     int32_t* labels, int32_t* sizes, uint64_t* pairs_bound, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !origin || !dims || !labels || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: null pointer");
+        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: ref_ld must be 3 or 6");
+        if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: radius must be finite and > 0");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: origin must be finite");
+        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: cell must be finite and > 0");
+        if (!((double)radius / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: radius / cell must be at most 8");
+        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
+        volatile float r2 = radius * radius;
+        const int R = pcc::rings(radius, cell);
+        if (!pcc::rings_suffice(g, r2, R))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the float32 faces of this grid do not separate cells " + std::to_string(R) +
+                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
+        if (workspace_bytes < pcc::layout(N, pcg::cells_of(g)).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: workspace smaller than ma_pc_cluster_workspace_bytes(N, nx, ny, nz)");
+        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        HIP_CHECK(pcc::launch_bound(ref, N, ref_ld, g, R, workspace, s));
+        unsigned long long total = 0;
+        HIP_CHECK(hipMemcpyAsync(&total, pcc::total_of(N, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (pairs_bound) *pairs_bound = total;
+        if (total > cap)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
+                                              ": use a smaller radius or fewer points");
+        HIP_CHECK(pcc::launch_hook_flatten(N, r2, g, labels, sizes, workspace, s));
     });
 }
 

@@ -21,6 +21,14 @@ def normalize_pc(pc_normal: np.ndarray) -> np.ndarray:
     return np.concatenate([pc_coor, normals], axis=-1, dtype=np.float16)
 
 
+def pc_frame(pc_normal: np.ndarray):
+    """(centre (3) float64, scale float64): the inverse of `normalize_pc`'s affine map on the same rows, x ~ centre + scale * normalised.
+    Computed in float64: centre = the bounding-box mid-point, scale = max |x - centre| / 0.9995."""
+    pc_coor = np.asarray(pc_normal)[:, :3].astype(np.float64)
+    centre = (pc_coor.min(axis=0) + pc_coor.max(axis=0)) / 2
+    return centre, float(np.abs(pc_coor - centre[None, :]).max() / 0.9995)
+
+
 def uid_of(input_path: str) -> str:
     """main.py:27,39: the sample's name, the file name up to its first dot."""
     return input_path.split("/")[-1].split(".")[0]
@@ -48,10 +56,21 @@ class Dataset:
     their K nearest neighbours exceeds the cloud's mean by more than outlier_std standard deviations are dropped, the survivors keep
     their order and stand in for the file's rows: the uniform draw or FPS runs over them, and pc_xyz takes its normals from their
     neighbours.  One stray row would otherwise set the scale of `normalize_pc`, and FPS picks strays first.  Fewer than n_points
-    survivors is a ValueError.  0 = off: no code path and no RNG draw changes.  With "mesh" a non-zero value is a ValueError."""
+    survivors is a ValueError.  0 = off: no code path and no RNG draw changes.  With "mesh" a non-zero value is a ValueError.
+
+    cluster_radius=R > 0 (pc_normal and pc_xyz; the reference has nothing like it): Euclidean clustering over the outlier filter's
+    survivors (pc_cluster.split_rows on the GPU, N <= 2^22, finite): the rows fall into the connected components of the graph that
+    links two rows at most R apart, and the components of fewer than cluster_min_points rows (>= n_points) are dropped: a floating
+    clump the outlier filter cannot see, or a second object.  Every kept component then stands in for the file's rows: the uniform
+    draw or FPS runs over it, and pc_xyz takes its normals from its rows alone.  cluster_mode "largest": the largest component only,
+    one item, uid unchanged.  "split": one item per kept component, adjacent, largest first, with uid "{uid}_part{j}" and the extra
+    keys "group" (the file's uid) and "part" (j); `__getitem__` adds "frame" = pc_frame of the item's rows, with which main.py maps
+    the part's mesh back into the file's coordinates.  No component of cluster_min_points rows is a ValueError.  0 = off: no code
+    path and no RNG draw changes, and the items keep exactly the keys above.  With "mesh" a non-zero value is a ValueError."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
-                 point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0):
+                 point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
+                 cluster_mode: str = "largest", cluster_min_points: int = 4096):
         self.data: List[Dict] = []
         if point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
@@ -62,19 +81,35 @@ class Dataset:
             if input_type == "mesh":
                 raise ValueError("outlier_k applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
             check_filter_args(outlier_k, outlier_std)                # before any file is read
+        if cluster_radius:
+            from .pc_cluster import check_split_args, split_rows
+            if input_type == "mesh":
+                raise ValueError("cluster_radius applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
+            check_split_args(cluster_radius, cluster_min_points, cluster_mode)
+            if cluster_min_points < n_points:
+                raise ValueError(f"cluster_min_points = {cluster_min_points} is less than the {n_points} rows the encoder takes")
+
+        def parts_of(cur_data, uid):
+            """[(rows of the file that stand in for it, the item's extra keys)]: the file itself, or its kept components"""
+            if not cluster_radius:
+                return [(cur_data, {"uid": uid})]
+            rows = split_rows(cur_data, cluster_radius, cluster_min_points, cluster_mode, uid, device=sample_device or "cuda")
+            if cluster_mode == "largest":
+                return [(cur_data[rows[0]], {"uid": uid})]
+            return [(cur_data[r], {"uid": f"{uid}_part{j}", "group": uid, "part": j}) for j, r in enumerate(rows)]
         if input_type == "pc_normal":
             for input_path in input_list:
                 cur_data = np.load(input_path)
                 if outlier_k:
                     cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
-                if point_sampling == "fps":
-                    from .pc_fps import fps_rows
-                    idx = fps_rows(cur_data, n_points, device=sample_device or "cuda")   # shape, length, finite: checked before the GPU is touched
-                else:
-                    assert cur_data.shape[0] >= n_points, "input pc_normal should have at least 4096 points"
-                    idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
-                cur_data = cur_data[idx]
-                self.data.append({"pc_normal": cur_data, "uid": uid_of(input_path)})
+                for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
+                    if point_sampling == "fps":
+                        from .pc_fps import fps_rows
+                        idx = fps_rows(cur_data, n_points, device=sample_device or "cuda")   # shape, length, finite: checked before the GPU is touched
+                    else:
+                        assert cur_data.shape[0] >= n_points, "input pc_normal should have at least 4096 points"
+                        idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
+                    self.data.append({"pc_normal": cur_data[idx], **keys})
         elif input_type == "mesh":
             # main.py:29-39 -> mesh_to_pc.py:42-57: load the file, draw n_points surface points + the normal of the face under each
             from .mesh_input import load_mesh, mesh_to_pc_normal
@@ -92,8 +127,8 @@ class Dataset:
                 cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
                 if outlier_k:
                     cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
-                self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling),
-                                  "uid": uid_of(input_path)})
+                for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
+                    self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling), **keys})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
         print(f"dataset total data samples: {len(self.data)}")
 
@@ -111,5 +146,18 @@ class Dataset:
     def __len__(self) -> int:
         return len(self.data)
 
+    def groups(self) -> List[int]:
+        """Per item the index of its group: the items of one file split into parts (cluster_mode "split") share one, adjacent; every
+        other item is a group of its own.  What dp.shard_grouped shards over."""
+        out: List[int] = []
+        for i, d in enumerate(self.data):
+            same = i > 0 and "group" in d and self.data[i - 1].get("group") == d["group"] and self.data[i - 1]["part"] + 1 == d["part"]
+            out.append(out[-1] if same else (out[-1] + 1 if out else 0))
+        return out
+
     def __getitem__(self, idx: int) -> Dict:
-        return {"pc_normal": normalize_pc(self.data[idx]["pc_normal"]), "uid": self.data[idx]["uid"]}
+        d = self.data[idx]
+        item = {"pc_normal": normalize_pc(d["pc_normal"]), "uid": d["uid"]}
+        if "group" in d:
+            item.update(group=d["group"], part=d["part"], frame=pc_frame(d["pc_normal"]))
+        return item

@@ -54,6 +54,15 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_items, world))
 
 
+def shard_grouped(groups: Sequence[int], rank: int, world: int) -> List[int]:
+    """groups[i]: the group of item i, the groups numbered 0, 1, ... in item order (data.Dataset.groups(): the parts of one file under
+    `--cluster_mode split` form a group).  Items owned by `rank`, in order: those of the groups g with g % world == rank, so that one
+    rank holds a whole group and can write its merged file.  With one item per group this is `shard_indices(len(groups), rank, world)`."""
+    if not (0 <= rank < world):
+        raise ValueError(f"rank {rank} outside world of {world}")
+    return [i for i, g in enumerate(groups) if int(g) % world == rank]
+
+
 def batches(indices: Sequence[int], batch_size: int) -> List[List[int]]:
     """DataLoader(batch_size, drop_last=False, shuffle=False) over a rank's shard (main.py:137-142)."""
     return [list(indices[i:i + batch_size]) for i in range(0, len(indices), batch_size)]

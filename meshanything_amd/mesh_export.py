@@ -132,6 +132,22 @@ def fix_normals(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
     return faces
 
 
+def merge_meshes(parts) -> Tuple[np.ndarray, np.ndarray]:
+    """parts: a sequence of (vertices (V_j, 3), faces (M_j, 3)) -> (vertices (sum V_j, 3) float64, faces (sum M_j, 3) int64): the parts one
+    after the other, the faces of part j offset by the vertices before it.  No vertices are merged across parts and every face keeps its
+    winding (`--cluster_mode split`: the parts of one input file in one OBJ).  An empty part adds nothing."""
+    verts, faces, offset = [np.zeros((0, 3), np.float64)], [np.zeros((0, 3), np.int64)], 0
+    for v, f in parts:
+        v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+        f = np.asarray(f, dtype=np.int64).reshape(-1, 3)
+        if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+            raise ValueError(f"a part's faces must index its own {v.shape[0]} vertices")
+        verts.append(v)
+        faces.append(f + offset)
+        offset += v.shape[0]
+    return np.concatenate(verts, 0), np.concatenate(faces, 0)
+
+
 FACE_COLOR = (255, 165, 0)                                   # main.py:170 (`brown_color`, alpha 255)
 
 

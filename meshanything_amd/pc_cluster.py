@@ -1,0 +1,178 @@
+"""Euclidean clustering of input clouds (`--cluster_radius`): split a cloud into the connected components of the graph that links two
+points when they are at most `radius` apart; PCL's EuclideanClusterExtraction is the same operation.
+
+The statistical outlier filter cannot see a floating clump of a few hundred points: it is locally as dense as the object.  Such a clump
+sets the scale of `data.normalize_pc` and farthest-point sampling picks it first; and a file that holds two objects is useless as one
+cloud to a model that meshes one object.  `euclidean_clusters` is the one call into the HIP library (csrc/pc_cluster.hpp; C ABI
+ma_op_pc_cluster, whose header comment states the contract): the cell grid of the outlier filter, a ring walk with an exact stop rule and
+a lock-free union-find; labels[i] is the smallest row of i's component, whatever the grid.  `choose_cluster_grid` fits the grid on the
+host, `components` and `split_rows` turn the labels into the parts `data.Dataset` makes items of.  It needs CUDA tensors; there is no CPU
+fallback.  There is no reference counterpart.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pc_normals import MAX_POINTS, _need_cuda
+from .pc_outliers import MAX_DIM, _check_grid, choose_grid
+
+MAX_PAIRS = 1 << 36                                              # MA_PC_CLUSTER_MAX_PAIRS
+MAX_RADIUS_IN_CELLS = 8                                          # ma_op_pc_cluster: radius / cell <= 8
+WANT = ("labels", "sizes")
+MODES = ("largest", "split")
+
+
+def check_radius(radius) -> float:
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (0.0 < float(radius) < float("inf")):
+        raise ValueError(f"radius must be finite and > 0, got {radius!r}")
+    if not np.isfinite(np.float32(radius)) or not np.float32(radius) > 0:
+        raise ValueError(f"radius must be a positive finite float32, got {radius!r}")
+    return float(radius)
+
+
+def choose_cluster_grid(xyz, radius):
+    """xyz (N, >= 3) host array, finite -> (origin (3) float32, cell float32, dims (3) int32) for `euclidean_clusters`: the box of
+    `pc_outliers.choose_grid` (the 1st to 99th percentile of a subsample, widened by one cell) with the number of cells along the longest
+    axis the largest that keeps cell >= radius, 128 at the most: a search then ends after two rings, and the cells hold as few points as
+    that allows.  choose_grid's cell is longest / (along - 2), so along = floor(longest / radius) + 2; capped at 128 the cell only grows,
+    and at most 128 cells an axis are at most 2^21 cells, so the limits always allow it.  A radius beyond the box's longest side: that
+    box at three cells an axis with cell = radius.  A box without extent: one cell.  A function of the array and the radius alone: no
+    random numbers.  The grid only decides the time."""
+    radius = check_radius(radius)
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] < 3 or xyz.shape[0] < 1:
+        raise ValueError(f"a point cloud must be a (N, >= 3) array, got {xyz.shape}")
+    r32 = np.float32(radius)
+    if float(r32) < radius:
+        r32 = np.nextafter(r32, np.float32(np.inf))
+    origin, longest, dims = choose_grid(xyz, 16, along=3)        # along = 3: the cell is the box's longest side
+    if int(dims.max()) == 1:                                     # one position, or nothing to fit to
+        return origin, np.float32(max(float(longest), float(r32))), dims
+    if float(longest) < radius:
+        return origin, r32, dims                                 # the same origin and dims with a larger cell: a larger box
+    along = int(min(math.floor(float(longest) / radius) + 2, MAX_DIM))
+    while True:
+        origin, cell, dims = choose_grid(xyz, 16, along=along)
+        if float(cell) >= radius or along <= 3:                  # (the float32 rounding of the cell can cost one step)
+            return origin, cell, dims
+        along -= 1
+
+
+def _check_cloud(points):
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] not in (3, 6):
+        raise ValueError(f"points must be a (N, 3) or (N, 6) tensor, got {tuple(points.shape) if hasattr(points, 'shape') else type(points).__name__}")
+    if points.dtype != torch.float32:
+        raise ValueError(f"points must be float32, got {points.dtype}")
+    if not 1 <= points.shape[0] <= MAX_POINTS:
+        raise ValueError(f"need 1 <= N <= 2^22 points, got N = {points.shape[0]}")
+
+
+def euclidean_clusters(points: torch.Tensor, radius, grid=None, want=("labels",), max_pairs=None):
+    """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns, finite -> a dict with the entries named in `want`: "labels"
+    (N) int32, labels[i] = the smallest row index in the connected component of i, rows i and j being linked iff
+    fl32(fl32(dx*dx + dy*dy) + dz*dz) <= fl32(radius * radius) (ma_op_pc_cluster), and "sizes" (N) int32, the number of rows of the
+    component at its root and 0 elsewhere.  grid: (origin, cell, dims) with radius / cell <= 8, None = `choose_cluster_grid` of the
+    points (copied to the host for it); the result does not depend on it.  max_pairs: the cap on the pair bound the library computes
+    before it searches (None = its own, 2^36); a bound above it is a ValueError that names both."""
+    radius = check_radius(radius)
+    _check_cloud(points)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in WANT for w in want):
+        raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
+    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
+        raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
+    if grid is not None:
+        grid = _check_grid(grid)
+        if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
+            raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
+    _need_cuda(points, "euclidean_clusters")
+    lib = _lib.load()
+    dev = points.device
+    with torch.cuda.device(dev):
+        ref = points.contiguous()
+        N = ref.shape[0]
+        if grid is None:
+            host = ref[:, :3].cpu().numpy()
+            if not np.isfinite(host).all():
+                raise ValueError("the point cloud has non-finite coordinates")
+            grid = choose_cluster_grid(host, radius)
+        origin, cell, dims = grid
+        nbytes = lib.ma_pc_cluster_workspace_bytes(N, int(dims[0]), int(dims[1]), int(dims[2]))
+        if nbytes == 0:
+            raise ValueError(f"outside the limits of ma_op_pc_cluster: N = {N}, dims = {dims.tolist()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        labels = torch.empty(N, dtype=torch.int32, device=dev)
+        sizes = torch.empty(N, dtype=torch.int32, device=dev) if "sizes" in want else None
+        bound = C.c_uint64(0)
+        cap = 0 if max_pairs is None else int(max_pairs)
+        rc = lib.ma_op_pc_cluster(ref.data_ptr(), N, ref.shape[1], radius, (C.c_float * 3)(*origin.tolist()), float(cell), (C.c_int32 * 3)(*dims.tolist()),
+                                  cap, labels.data_ptr(), None if sizes is None else sizes.data_ptr(), C.byref(bound), ws.data_ptr(), nbytes,
+                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != _lib.MA_OK and bound.value > (cap or MAX_PAIRS):
+            raise ValueError(f"euclidean_clusters: the pair bound {bound.value} exceeds max_pairs {cap or MAX_PAIRS} (N = {N}, radius {radius}): "
+                             "use a smaller radius or fewer points")
+        _lib.check(rc)
+    out = {"labels": labels, "sizes": sizes}
+    return {w: out[w] for w in WANT if w in want}
+
+
+def components(labels):
+    """labels (N) host integers -> (roots (C), counts (C)) int64, ordered by count descending, then root ascending."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"labels must be a (N) integer array, got {labels.shape} {labels.dtype}")
+    roots, counts = np.unique(labels.astype(np.int64), return_counts=True)
+    order = np.lexsort((roots, -counts))
+    return roots[order], counts[order].astype(np.int64)
+
+
+def check_split_args(radius, min_points, mode) -> tuple:
+    """The checks on (radius, min_points, mode); returns them as (float, int, str)."""
+    radius = check_radius(radius)
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or int(min_points) < 1:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    return radius, int(min_points), mode
+
+
+def check_cluster_cloud(xyz) -> np.ndarray:
+    """The checks of split_rows on the cloud that need no device; returns xyz as an array."""
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
+        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
+    if not 1 <= xyz.shape[0] <= MAX_POINTS:
+        raise ValueError(f"clustering needs 1 <= N <= 2^22 points, got N = {xyz.shape[0]}")
+    if not np.isfinite(xyz[:, :3]).all():
+        raise ValueError("the point cloud has non-finite coordinates")
+    return xyz
+
+
+def split_rows(xyz, radius, min_points, mode, uid: str, device="cuda"):
+    """xyz (N, >= 3) host array, only the first three columns are read (uploaded as float32) -> a list of row-index arrays (int64), one
+    per kept component: the components of `euclidean_clusters` with at least min_points rows, in the order of `components`, each in the
+    file's row order; mode "largest" keeps the first only.  Prints the clustering line of the command line.  No component of
+    min_points rows is a ValueError that names the largest size."""
+    radius, min_points, mode = check_split_args(radius, min_points, mode)
+    xyz = check_cluster_cloud(xyz)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("split_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    host = np.ascontiguousarray(xyz[:, :3], dtype=np.float32)
+    grid = choose_cluster_grid(host, radius)
+    with torch.cuda.device(dev):
+        labels = euclidean_clusters(torch.from_numpy(host).to(dev), radius, grid)["labels"].cpu().numpy()
+    roots, counts = components(labels)
+    if int(counts[0]) < min_points:
+        raise ValueError(f"{uid}: clustering (radius {radius:g}) found no component of {min_points} points: the largest of {roots.shape[0]} has {int(counts[0])}")
+    keep = int((counts >= min_points).sum()) if mode == "split" else 1
+    parts = [np.flatnonzero(labels == roots[c]) for c in range(keep)]
+    kept = int(counts[:keep].sum())
+    print(f"{uid}: clustering (radius {radius:g}) found {roots.shape[0]} components, kept {keep} (sizes {' '.join(str(int(c)) for c in counts[:keep])}), "
+          f"dropped {xyz.shape[0] - kept} of {xyz.shape[0]} points")
+    return parts
