@@ -612,6 +612,44 @@ MA_API int    ma_op_pc_cluster(const float *ref, int N, int ref_ld, float radius
                                void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz);
 
+/* ---- Dominant planes: RANSAC hypothesis scoring and one plane applied, for --plane_threshold (csrc/pc_plane.hpp).  Has no reference
+ * counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays
+ * (`plane` is a HOST array of six floats), caller-owned workspace, asynchronous on `stream`.
+ *
+ * The inlier rule, shared by both calls.  A plane is six float32, a point a and a normal n of any length.  With no FMA contraction:
+ *       len2 = fl32(fl32(nx*nx + ny*ny) + nz*nz),  rhs = fl32(t2 * len2),  t2 = fl32(threshold * threshold) computed once on the host
+ *       d = fl32(p - a) per axis,  s = fl32(fl32(fl32(nx*dx) + fl32(ny*dy)) + fl32(nz*dz))
+ *       row p is an INLIER iff fl32(s*s) <= rhs
+ *   Equality is included.  There is no square root and no division, so a numpy float32 restatement gives the same bits.  A plane is
+ *   DEGENERATE iff !(len2 > 0) or rhs is not finite; a degenerate plane has no inliers.  A NaN or infinite row is never an inlier.
+ *
+ * ma_op_pc_plane_score: ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6; tri (H, 3) int32, the rows (i, j, k) of
+ *   hypothesis h.  Its plane: a = p_i, e1 = fl32(p_j - p_i), e2 = fl32(p_k - p_i), n = e1 x e2 with every product and difference rounded
+ *   separately, nx = fl32(fl32(e1y*e2z) - fl32(e1z*e2y)) and cyclically.  A triple with an index outside [0, N) is degenerate, nothing
+ *   is read out of bounds, and its plane is six zeros.  planes (H, 6) fp32 or NULL: (a, n) per hypothesis.  counts (H) int32: the number
+ *   of inlier rows, -1 for a degenerate hypothesis.  best (1) int32: the h with the greatest count, the lowest index among equals, -1 if
+ *   every hypothesis is degenerate.  The counts are sums of integer atomics, which add in any order to the same value: the outputs are a
+ *   function of the inputs alone, EQUAL to the restatement's and identical on a second run.
+ *   3 <= N <= MA_PC_PLANE_MAX_POINTS, 1 <= H <= MA_PC_PLANE_MAX_HYPOTHESES, threshold finite and > 0.
+ *
+ * ma_op_pc_plane_apply: one plane against every row.  mask (N) uint8, 1 = inlier, exact under the rule; count (1) int32 = the mask's
+ *   sum; moments (10) float64 over the inliers with q = (double)p - (double)a: n, Sqx, Sqy, Sqz, Sqxqx, Sqxqy, Sqxqz, Sqyqy, Sqyqz,
+ *   Sqzqz.  Each of the three may be NULL, at least one must be given.  The moments come from a reduction of fixed shape, per-workgroup
+ *   partials (a fixed tree over 256 threads of 4 rows each) and one pass over the partials in index order; no floating-point atomics, so
+ *   two runs give the same bits.  Equality with another summation order is NOT claimed: |got - want| <= n * 2^-52 * S|term| per moment,
+ *   the worst case for any order of n float64 terms.  A degenerate plane gives an all-zero mask, count 0 and zero moments.
+ *   3 <= N <= MA_PC_PLANE_MAX_POINTS, threshold finite and > 0; the workspace of ma_pc_plane_workspace_bytes(N, 1) suffices.
+ *
+ * workspace: ma_pc_plane_workspace_bytes(N, H) bytes of device memory (0 for arguments outside the limits): the apply partials and the
+ *   eight floats per hypothesis; its contents on entry do not matter. */
+#define MA_PC_PLANE_MAX_POINTS      (1 << 22)
+#define MA_PC_PLANE_MAX_HYPOTHESES  (1 << 16)
+MA_API int    ma_op_pc_plane_score(const float *ref, int N, int ref_ld, const int32_t *tri, int H, float threshold, float *planes /* or NULL */,
+                                   int32_t *counts, int32_t *best, void *workspace, size_t workspace_bytes, void *stream);
+MA_API int    ma_op_pc_plane_apply(const float *ref, int N, int ref_ld, const float *plane /* host, 6 */, float threshold, uint8_t *mask /* or NULL */,
+                                   int32_t *count /* or NULL */, double *moments /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_plane_workspace_bytes(int N, int H);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,13 @@ state later stages see differs from a `--point_sampling random` run.
 their K nearest neighbours exceeds the cloud's mean by more than `--outlier_std` standard deviations, found on the GPU over a cell grid
 (`meshanything_amd/pc_outliers.py`); sampling and normal estimation then see the survivors only, and one line per input reports how many
 rows went.
+`--plane_threshold T` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) then removes the dominant plane,
+the table, floor or wall a scanned object stands on: `--plane_iters` RANSAC hypotheses (default 1024, 1..65536), three rows each from a
+private generator (the numpy RNG is not touched), are scored against every row on the GPU (`meshanything_amd/pc_plane.py`), the plane that
+holds the most rows within T is refitted to them and its inliers are dropped, `--plane_count` times (default 1, 1..8).  A best plane that
+holds fewer than `--plane_min_fraction` of the rows (default 0.2, in (0, 1]) ends the search: 1024 draws find a plane of 0.2 of the rows
+with probability 1 - 2.7e-4, one of 0.1 only with 0.64, so raise `--plane_iters` when you lower the floor.  An object's own large flat
+face is a plane too; the floor and the opt-in are the only guard.  One line per input reports the planes.
 `--cluster_radius R` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) then splits what is left into the
 connected parts of the graph that links two points at most R apart, on the GPU over the same cell grid (`meshanything_amd/pc_cluster.py`),
 and drops the parts of fewer than `--cluster_min_points` points (default and least 4096): a floating clump the outlier filter cannot see,
@@ -83,7 +90,32 @@ def get_args(argv=None):
                    help="with --cluster_radius: mesh the largest part only (the default), or every kept part, written in the input's coordinates")
     p.add_argument("--cluster_min_points", default=None, type=int,
                    help="with --cluster_radius: drop the parts of fewer points than this (default 4096, the rows the encoder takes)")
+    p.add_argument("--plane_threshold", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: remove the dominant plane (a table, a floor) before clustering: the rows within this "
+                        "distance of it, in the units of the input file (0 = off)")
+    p.add_argument("--plane_iters", default=None, type=int,
+                   help="with --plane_threshold: RANSAC hypotheses per plane (1..65536, default 1024); raise it when you lower --plane_min_fraction: a plane "
+                        "holding a fraction w of the rows is missed by n draws with probability (1 - w^3)^n")
+    p.add_argument("--plane_count", default=None, type=int, help="with --plane_threshold: remove up to this many planes, one after the other (1..8, default 1)")
+    p.add_argument("--plane_min_fraction", default=None, type=float,
+                   help="with --plane_threshold: stop when the best plane holds less than this fraction of the remaining rows (in (0, 1], default 0.2)")
     args = p.parse_args(argv)
+    if not (0.0 <= args.plane_threshold < float("inf")):
+        p.error("--plane_threshold must be finite and >= 0 (0 = off)")
+    others = args.plane_iters is not None or args.plane_count is not None or args.plane_min_fraction is not None
+    if args.input_type == "mesh" and (args.plane_threshold != 0 or others):
+        p.error("--plane_threshold, --plane_iters, --plane_count and --plane_min_fraction apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+    if args.plane_threshold == 0 and others:
+        p.error("--plane_iters, --plane_count and --plane_min_fraction need --plane_threshold > 0")
+    if args.plane_iters is not None and not 1 <= args.plane_iters <= 65536:
+        p.error("--plane_iters must be in 1..65536")
+    if args.plane_count is not None and not 1 <= args.plane_count <= 8:
+        p.error("--plane_count must be in 1..8")
+    if args.plane_min_fraction is not None and not (0.0 < args.plane_min_fraction <= 1.0):
+        p.error("--plane_min_fraction must be in (0, 1]")
+    args.plane_iters = 1024 if args.plane_iters is None else args.plane_iters
+    args.plane_count = 1 if args.plane_count is None else args.plane_count
+    args.plane_min_fraction = 0.2 if args.plane_min_fraction is None else args.plane_min_fraction
     if not (0.0 <= args.cluster_radius < float("inf")):
         p.error("--cluster_radius must be finite and >= 0 (0 = off)")
     if args.input_type == "mesh" and (args.cluster_radius != 0 or args.cluster_mode is not None or args.cluster_min_points is not None):
@@ -163,7 +195,8 @@ def main():
     else:
         dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling,
                           outlier_k=args.outlier_k, outlier_std=args.outlier_std, cluster_radius=args.cluster_radius, cluster_mode=args.cluster_mode,
-                          cluster_min_points=args.cluster_min_points)
+                          cluster_min_points=args.cluster_min_points, plane_threshold=args.plane_threshold, plane_iters=args.plane_iters,
+                          plane_count=args.plane_count, plane_min_fraction=args.plane_min_fraction)
 
     begin = time.time()
     print("Generation Start!!!")

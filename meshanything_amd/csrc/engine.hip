@@ -45,6 +45,7 @@
 #include "pc_fps.hpp"
 #include "pc_grid.hpp"
 #include "pc_cluster.hpp"
+#include "pc_plane.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1164,6 +1165,41 @@ int ma_op_pc_cluster(const float* ref, int N, int ref_ld, float radius, const fl
             throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
                                               ": use a smaller radius or fewer points");
         HIP_CHECK(pcc::launch_hook_flatten(N, r2, g, labels, sizes, workspace, s));
+    });
+}
+
+// ---- dominant planes: hypothesis scoring and one plane applied (csrc/pc_plane.hpp) ----------------------------------------------------------
+static bool pc_plane_shape_ok(int N, int H) { return N >= 3 && N <= MA_PC_PLANE_MAX_POINTS && H >= 1 && H <= MA_PC_PLANE_MAX_HYPOTHESES; }
+
+size_t ma_pc_plane_workspace_bytes(int N, int H) { return pc_plane_shape_ok(N, H) ? pcp::layout(N, H).bytes : 0; }
+
+int ma_op_pc_plane_score(const float* ref, int N, int ref_ld, const int32_t* tri, int H, float threshold, float* planes, int32_t* counts, int32_t* best,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !tri || !counts || !best || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_score: null pointer");
+        if (!pc_plane_shape_ok(N, H)) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_score: need 3 <= N <= 2^22 and 1 <= H <= 2^16");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_score: ref_ld must be 3 or 6");
+        if (!std::isfinite(threshold) || !(threshold > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_score: threshold must be finite and > 0");
+        if (workspace_bytes < pcp::layout(N, H).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_score: workspace smaller than ma_pc_plane_workspace_bytes(N, H)");
+        volatile float t2 = threshold * threshold;
+        HIP_CHECK(pcp::launch_score(ref, N, ref_ld, tri, H, t2, planes, counts, best, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_plane_apply(const float* ref, int N, int ref_ld, const float* plane, float threshold, uint8_t* mask, int32_t* count, double* moments,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !plane || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: null pointer");
+        if (!mask && !count && !moments) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: at least one of mask, count and moments must be given");
+        if (!pc_plane_shape_ok(N, 1)) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: need 3 <= N <= 2^22");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: ref_ld must be 3 or 6");
+        if (!std::isfinite(threshold) || !(threshold > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: threshold must be finite and > 0");
+        if (workspace_bytes < pcp::layout(N, 1).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_plane_apply: workspace smaller than ma_pc_plane_workspace_bytes(N, 1)");
+        volatile float t2 = threshold * threshold;
+        const pcp::Plane pl{plane[0], plane[1], plane[2], plane[3], plane[4], plane[5], pcp::plane_rhs(plane[3], plane[4], plane[5], t2)};
+        HIP_CHECK(pcp::launch_apply(ref, N, ref_ld, pl, mask, count, moments, workspace, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

@@ -66,11 +66,22 @@ class Dataset:
     one item, uid unchanged.  "split": one item per kept component, adjacent, largest first, with uid "{uid}_part{j}" and the extra
     keys "group" (the file's uid) and "part" (j); `__getitem__` adds "frame" = pc_frame of the item's rows, with which main.py maps
     the part's mesh back into the file's coordinates.  No component of cluster_min_points rows is a ValueError.  0 = off: no code
-    path and no RNG draw changes, and the items keep exactly the keys above.  With "mesh" a non-zero value is a ValueError."""
+    path and no RNG draw changes, and the items keep exactly the keys above.  With "mesh" a non-zero value is a ValueError.
+
+    plane_threshold=T > 0 (pc_normal and pc_xyz; the reference has nothing like it): dominant-plane removal AFTER the outlier filter and
+    BEFORE clustering (pc_plane.remove_planes on the GPU, N <= 2^22, finite): up to plane_count times, plane_iters RANSAC hypotheses from
+    a private generator are scored against the rows still kept, the one that holds the most rows within T (file units) is refitted to
+    them and its inliers are dropped; a best plane that holds fewer than plane_min_fraction of the rows ends the search.  That is the
+    table, floor or wall a scanned object stands on: as dense as the object, so the outlier filter keeps it, and in touch with it, so
+    clustering cannot part them.  The survivors keep their order and stand in for the file's rows.  An object's own large flat face is
+    a plane too: the floor plane_min_fraction and the opt-in are the only guard.  Fewer than n_points survivors is a ValueError.
+    0 = off: no code path and no draw from the numpy RNG changes (the hypotheses never use the global RNG).  With "mesh" a non-zero
+    value is a ValueError."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
-                 cluster_mode: str = "largest", cluster_min_points: int = 4096):
+                 cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
+                 plane_count: int = 1, plane_min_fraction: float = 0.2):
         self.data: List[Dict] = []
         if point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
@@ -81,6 +92,11 @@ class Dataset:
             if input_type == "mesh":
                 raise ValueError("outlier_k applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
             check_filter_args(outlier_k, outlier_std)                # before any file is read
+        if plane_threshold:
+            from .pc_plane import check_remove_args, remove_planes
+            if input_type == "mesh":
+                raise ValueError("plane_threshold applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
+            check_remove_args(plane_threshold, plane_iters, plane_count, plane_min_fraction)   # before any file is read
         if cluster_radius:
             from .pc_cluster import check_split_args, split_rows
             if input_type == "mesh":
@@ -102,6 +118,9 @@ class Dataset:
                 cur_data = np.load(input_path)
                 if outlier_k:
                     cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
+                if plane_threshold:
+                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, n_points, uid_of(input_path),
+                                                      device=sample_device or "cuda")]
                 for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
                     if point_sampling == "fps":
                         from .pc_fps import fps_rows
@@ -127,6 +146,9 @@ class Dataset:
                 cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
                 if outlier_k:
                     cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
+                if plane_threshold:
+                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, n_points, uid_of(input_path),
+                                                      device=sample_device or "cuda")]
                 for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
                     self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling), **keys})
         # any other value yields an empty dataset, like the reference's default 'pc' (main.py:70-75)
