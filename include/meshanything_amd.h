@@ -612,6 +612,51 @@ MA_API int    ma_op_pc_cluster(const float *ref, int N, int ref_ld, float radius
                                void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz);
 
+/* ---- Moving-least-squares smoothing: every row onto the plane fitted to its radius neighbourhood, for --smooth_radius
+ * (csrc/pc_smooth.hpp); PCL's MovingLeastSquares without the polynomial.  Has no reference counterpart.  Needs no engine; errors via
+ * ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays (origin, dims and pair_bound are HOST
+ * pointers), caller-owned workspace.  NOT asynchronous: the call reads the pair bound back on `stream` before it launches the long
+ * kernel, as ma_op_pc_cluster does.
+ *
+ * ma_op_pc_smooth: ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6; r2 = fl32(radius * radius), computed once on
+ *   the host.  For row i at position q:
+ *   Neighbours: every row j, i itself included, with
+ *       d = fl32(fl32(dx * dx + dy * dy) + dz * dz) <= r2,  dx = fl32(q_x - x_j), dy = fl32(q_y - y_j), dz = fl32(q_z - z_j)
+ *   (the key of ma_op_pc_knn and the link rule of ma_op_pc_cluster, no FMA contraction; a NaN key is not a neighbour; equality is
+ *   included).  count (N) int32 = the number of neighbours: a function of the cloud and the radius alone, EQUAL to a brute force.
+ *   Weights, float64, no contraction: s = (double)d / (double)r2, u = 1 - s, w = (u * u) * u.  A polynomial, so every term is exact IEEE
+ *   arithmetic that a numpy restatement reproduces bit for bit; it is 0 at the rim, so a row whose key equals r2 changes count alone.
+ *   Moments over the neighbours with e = ((double)dx, (double)dy, (double)dz), the differences of the key: S0 = sum w, S1 = sum w * e,
+ *   S2_ab = sum (w * e_a) * e_b (six entries), summed in the order the walk visits the rows.  That order depends on the grid and, inside
+ *   a cell, on the order the build's atomics resolved in: the float outputs are NOT bit-reproducible, they agree with any other
+ *   summation order to what float64 resolves (DESIGN.md section 17 has the measured figures).
+ *   Plane: mu = S1 / S0, C = S2 / S0 - mu mu^T; the cyclic Jacobi of ma_op_pc_normals; eigvals (N, 3) float64 ascending; normals (N, 3)
+ *   float64 = the unit eigenvector of the smallest, its component of largest magnitude positive, the lowest axis on ties.
+ *   Projection onto the plane through the weighted centroid q - mu: t = (mu_x * n_x + mu_y * n_y) + mu_z * n_z, moved (N, 3) float64 =
+ *   (double)q - t * n per component.  |moved - q| <= |mu| <= radius.
+ *   A row STAYS where it is -- moved = (double)q, normal (0, 0, 1), eigenvalues 0 -- if count < min_count, if all its neighbours
+ *   coincide, or if anything comes out non-finite; such a row is recognisable from count and the eigenvalues.
+ *   No polynomial (order-2) fit is made: a plane projection shrinks a curved surface by roughly radius^2 / (8 * its radius of
+ *   curvature) and rounds an edge over a width of the radius.
+ *   Each of moved, normals, eigvals and count may be NULL, at least one must be given; outputs are in the ORIGINAL row order and no
+ *   neighbour list is ever written to memory.
+ *   The grid (origin, cell, dims: as for ma_op_pc_knn_grid, the same faces and cell rule) only decides the time and the summation
+ *   order; the walk and its stop rule are ma_op_pc_cluster's.  The pair bound is ma_op_pc_cluster's too: computed before the long
+ *   kernel, written to *pair_bound (if given), and if it exceeds max_pairs (0 = MA_PC_CLUSTER_MAX_PAIRS) the call fails with
+ *   MA_ERR_INVALID, the message giving both numbers, launches nothing further and writes no output.  A grid whose float32 faces would
+ *   break the bound is refused with MA_ERR_INVALID before any device work.
+ *   Non-finite coordinates: such a row has no neighbour and stays; nothing is read or written out of bounds.
+ *   1 <= N <= MA_PC_GRID_MAX_POINTS, radius finite and > 0, MA_PC_SMOOTH_MIN_COUNT <= min_count, the grid limits of ma_op_pc_knn_grid,
+ *   radius / cell <= 8.  workspace: ma_pc_smooth_workspace_bytes(N, nx, ny, nz) bytes of device memory (0 for arguments outside those
+ *   limits): the grid's layout and the 8-byte total; its contents on entry do not matter. */
+#define MA_PC_SMOOTH_MIN_COUNT 3
+MA_API int    ma_op_pc_smooth(const float *ref, int N, int ref_ld, float radius, const float *origin, float cell, const int32_t *dims,
+                              int min_count, uint64_t max_pairs /* 0 = MA_PC_CLUSTER_MAX_PAIRS */, double *moved /* or NULL */,
+                              double *normals /* or NULL */, double *eigvals /* or NULL */, int32_t *count /* or NULL */,
+                              uint64_t *pair_bound /* host pointer or NULL: the bound that was computed */,
+                              void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_smooth_workspace_bytes(int N, int nx, int ny, int nz);
+
 /* ---- Dominant planes: RANSAC hypothesis scoring and one plane applied, for --plane_threshold (csrc/pc_plane.hpp).  Has no reference
  * counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays
  * (`plane` is a HOST array of six floats), caller-owned workspace, asynchronous on `stream`.

@@ -37,6 +37,12 @@ or a second object; one line per input reports the parts.  `--cluster_mode large
 `--cluster_mode split` meshes every kept part as a row of the batch, writes `{uid}_part{j}_gen.obj` in the INPUT's coordinates (centre +
 scale * 2 * v, the inverse of the normalisation) and, after a file's last part, `{uid}_gen.obj`: the parts one after the other, no vertex
 merged across them.  The parts of one file stay on one rank (`dp.shard_grouped`).
+`--smooth_radius R` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) smooths what is left, last of the
+cleaning steps and once per kept part: every point is projected onto the plane fitted to the points within R of it, weights
+(1 - d^2 / R^2)^3, on the GPU over the same cell grid (`meshanything_amd/pc_smooth.py`), `--smooth_iters` times (1..8, default 1), and a
+pc_normal file's normals are replaced by the fitted ones on the file's side; sampling and the pc_xyz normal estimate then see the smoothed
+points, and one line per input reports how far they moved.  It removes measurement noise on the surface itself, which no other step touches.
+A plane fit shrinks a curved surface by roughly R^2 / (8 * its radius of curvature) and rounds edges over a width of R.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -99,7 +105,20 @@ def get_args(argv=None):
     p.add_argument("--plane_count", default=None, type=int, help="with --plane_threshold: remove up to this many planes, one after the other (1..8, default 1)")
     p.add_argument("--plane_min_fraction", default=None, type=float,
                    help="with --plane_threshold: stop when the best plane holds less than this fraction of the remaining rows (in (0, 1], default 0.2)")
+    p.add_argument("--smooth_radius", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: smooth the input last of the cleaning steps: project every point onto the plane fitted to "
+                        "the points within this distance of it, in the units of the input file (0 = off)")
+    p.add_argument("--smooth_iters", default=None, type=int, help="with --smooth_radius: smoothing passes (1..8, default 1)")
     args = p.parse_args(argv)
+    if not (0.0 <= args.smooth_radius < float("inf")):
+        p.error("--smooth_radius must be finite and >= 0 (0 = off)")
+    if args.input_type == "mesh" and (args.smooth_radius != 0 or args.smooth_iters is not None):
+        p.error("--smooth_radius and --smooth_iters apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+    if args.smooth_radius == 0 and args.smooth_iters is not None:
+        p.error("--smooth_iters needs --smooth_radius > 0")
+    if args.smooth_iters is not None and not 1 <= args.smooth_iters <= 8:
+        p.error("--smooth_iters must be in 1..8")
+    args.smooth_iters = 1 if args.smooth_iters is None else args.smooth_iters
     if not (0.0 <= args.plane_threshold < float("inf")):
         p.error("--plane_threshold must be finite and >= 0 (0 = off)")
     others = args.plane_iters is not None or args.plane_count is not None or args.plane_min_fraction is not None
@@ -196,7 +215,8 @@ def main():
         dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling,
                           outlier_k=args.outlier_k, outlier_std=args.outlier_std, cluster_radius=args.cluster_radius, cluster_mode=args.cluster_mode,
                           cluster_min_points=args.cluster_min_points, plane_threshold=args.plane_threshold, plane_iters=args.plane_iters,
-                          plane_count=args.plane_count, plane_min_fraction=args.plane_min_fraction)
+                          plane_count=args.plane_count, plane_min_fraction=args.plane_min_fraction, smooth_radius=args.smooth_radius,
+                          smooth_iters=args.smooth_iters)
 
     begin = time.time()
     print("Generation Start!!!")

@@ -45,6 +45,7 @@
 #include "pc_fps.hpp"
 #include "pc_grid.hpp"
 #include "pc_cluster.hpp"
+#include "pc_smooth.hpp"
 #include "pc_plane.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
@@ -1165,6 +1166,46 @@ int ma_op_pc_cluster(const float* ref, int N, int ref_ld, float radius, const fl
             throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
                                               ": use a smaller radius or fewer points");
         HIP_CHECK(pcc::launch_hook_flatten(N, r2, g, labels, sizes, workspace, s));
+    });
+}
+
+// ---- moving-least-squares smoothing over the cell grid (csrc/pc_smooth.hpp) -----------------------------------------------------------------
+size_t ma_pc_smooth_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcs::layout(N, nx * ny * nz).bytes : 0; }
+
+int ma_op_pc_smooth(const float* ref, int N, int ref_ld, float radius, const float* origin, float cell, const int32_t* dims, int min_count,
+                    uint64_t max_pairs, double* moved, double* normals, double* eigvals, int32_t* count, uint64_t* pair_bound, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !origin || !dims || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: null pointer");
+        if (!moved && !normals && !eigvals && !count)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: no output: give at least one of moved, normals, eigvals and count");
+        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: ref_ld must be 3 or 6");
+        if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: radius must be finite and > 0");
+        if (min_count < pcs::MIN_COUNT) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: min_count must be at least 3, the points a plane takes");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: origin must be finite");
+        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: cell must be finite and > 0");
+        if (!((double)radius / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: radius / cell must be at most 8");
+        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
+        volatile float r2 = radius * radius;
+        const int R = pcc::rings(radius, cell);
+        if (!pcc::rings_suffice(g, r2, R))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: the float32 faces of this grid do not separate cells " + std::to_string(R) +
+                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
+        if (workspace_bytes < pcs::layout(N, pcg::cells_of(g)).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: workspace smaller than ma_pc_smooth_workspace_bytes(N, nx, ny, nz)");
+        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        HIP_CHECK(pcs::launch_bound(ref, N, ref_ld, g, R, workspace, s));
+        unsigned long long total = 0;
+        HIP_CHECK(hipMemcpyAsync(&total, pcs::total_of(N, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (pair_bound) *pair_bound = total;
+        if (total > cap)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
+                                              ": use a smaller radius or fewer points");
+        HIP_CHECK(pcs::launch_smooth(N, r2, g, min_count, moved, normals, eigvals, count, workspace, s));
     });
 }
 

@@ -175,6 +175,32 @@ __device__ inline void rotate(double& app, double& aqq, double& apq, double& arp
 
 constexpr int JACOBI_SWEEPS = 12;    // a 3x3 converges quadratically: 4 to 6 sweeps in practice
 
+// The symmetric 3x3 (a00 a01 a02; a01 a11 a12; a02 a12 a22) by cyclic Jacobi, float64, no FMA contraction: its eigenvalues ascending (the
+// lower axis first among equals) and the unit eigenvector of the smallest, signed so that its component of largest magnitude is positive
+// (lowest axis on ties).  Shared by normals_kernel and the smoothing kernel of pc_smooth.hpp; non-finite input gives non-finite output.
+__device__ inline void smallest_eigenvector(double a00, double a11, double a22, double a01, double a02, double a12, double& l0, double& l1, double& l2,
+                                            double& nx, double& ny, double& nz) {
+#pragma clang fp contract(off)
+    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+        if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
+        rotate(a00, a11, a01, a02, a12, v0, v1);                    // (0, 1), third axis 2
+        rotate(a00, a22, a02, a01, a12, v0, v2);                    // (0, 2), third axis 1
+        rotate(a11, a22, a12, a01, a02, v1, v2);                    // (1, 2), third axis 0
+    }
+    // ascending, the lower axis first among equals; n = the column of the smallest
+    l0 = a00; l1 = a11; l2 = a22;
+    nx = v0[0]; ny = v0[1]; nz = v0[2];
+    if (l1 < l0) { const double t = l0; l0 = l1; l1 = t; nx = v1[0]; ny = v1[1]; nz = v1[2]; }
+    if (l2 < l0) { const double t = l0; l0 = l2; l2 = t; nx = v2[0]; ny = v2[1]; nz = v2[2]; }
+    if (l2 < l1) { const double t = l1; l1 = l2; l2 = t; }
+    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+    nx /= len; ny /= len; nz /= len;
+    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+    const double lead = ax >= ay && ax >= az ? nx : (ay >= az ? ny : nz);
+    if (lead < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+}
+
 __global__ __launch_bounds__(Q_THREADS) void normals_kernel(const float* __restrict__ ref, int N, int ref_ld, const int* __restrict__ nbr_idx, int Q,
                                                             int k, double* __restrict__ normals, double* __restrict__ eigvals) {
 #pragma clang fp contract(off)
@@ -200,24 +226,8 @@ __global__ __launch_bounds__(Q_THREADS) void normals_kernel(const float* __restr
         a01 += dx * dy; a02 += dx * dz; a12 += dy * dz;
     }
     a00 /= (double)k; a11 /= (double)k; a22 /= (double)k; a01 /= (double)k; a02 /= (double)k; a12 /= (double)k;
-    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};
-    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-        if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
-        rotate(a00, a11, a01, a02, a12, v0, v1);                    // (0, 1), third axis 2
-        rotate(a00, a22, a02, a01, a12, v0, v2);                    // (0, 2), third axis 1
-        rotate(a11, a22, a12, a01, a02, v1, v2);                    // (1, 2), third axis 0
-    }
-    // ascending, the lower axis first among equals; n = the column of the smallest
-    double l0 = a00, l1 = a11, l2 = a22;
-    double nx = v0[0], ny = v0[1], nz = v0[2];
-    if (l1 < l0) { const double t = l0; l0 = l1; l1 = t; nx = v1[0]; ny = v1[1]; nz = v1[2]; }
-    if (l2 < l0) { const double t = l0; l0 = l2; l2 = t; nx = v2[0]; ny = v2[1]; nz = v2[2]; }
-    if (l2 < l1) { const double t = l1; l1 = l2; l2 = t; }
-    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
-    nx /= len; ny /= len; nz /= len;
-    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
-    const double lead = ax >= ay && ax >= az ? nx : (ay >= az ? ny : nz);
-    if (lead < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+    double l0, l1, l2, nx, ny, nz;
+    smallest_eigenvector(a00, a11, a22, a01, a02, a12, l0, l1, l2, nx, ny, nz);
     const bool finite = isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(l0) && isfinite(l1) && isfinite(l2);
     if (same || !finite) {                                          // coincident neighbours (or coordinates that overflow): no plane to fit
         nx = 0.0; ny = 0.0; nz = 1.0;

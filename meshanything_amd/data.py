@@ -76,12 +76,20 @@ class Dataset:
     clustering cannot part them.  The survivors keep their order and stand in for the file's rows.  An object's own large flat face is
     a plane too: the floor plane_min_fraction and the opt-in are the only guard.  Fewer than n_points survivors is a ValueError.
     0 = off: no code path and no draw from the numpy RNG changes (the hypotheses never use the global RNG).  With "mesh" a non-zero
-    value is a ValueError."""
+    value is a ValueError.
+
+    smooth_radius=R > 0 (pc_normal and pc_xyz; the reference has nothing like it): moving-least-squares smoothing, the LAST of the cleaning
+    steps and before sampling (pc_smooth.smooth_rows on the GPU, N <= 2^22, finite), once per kept part: every row that stands in for the
+    file is projected onto the plane fitted to the rows within R of it (file units), smooth_iters times (1..8), and a file's normals are
+    replaced by the fitted ones on the file's side.  The strays and the table are gone by then and cannot pull the fit.  The uniform draw
+    or FPS then runs over the smoothed rows, and pc_xyz estimates its normals from them.  A plane fit shrinks a curved surface by roughly
+    R^2 / (8 * its radius of curvature) and rounds edges over a width of R.  0 = off: no code path, key, print or RNG draw changes.
+    With "mesh" a non-zero value is a ValueError."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
                  cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
-                 plane_count: int = 1, plane_min_fraction: float = 0.2):
+                 plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1):
         self.data: List[Dict] = []
         if point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
@@ -104,9 +112,19 @@ class Dataset:
             check_split_args(cluster_radius, cluster_min_points, cluster_mode)
             if cluster_min_points < n_points:
                 raise ValueError(f"cluster_min_points = {cluster_min_points} is less than the {n_points} rows the encoder takes")
+        if smooth_radius:
+            from .pc_smooth import check_smooth_args, smooth_rows
+            if input_type == "mesh":
+                raise ValueError("smooth_radius applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
+            check_smooth_args(smooth_radius, smooth_iters)           # before any file is read
 
         def parts_of(cur_data, uid):
-            """[(rows of the file that stand in for it, the item's extra keys)]: the file itself, or its kept components"""
+            """[(rows of the file that stand in for it, the item's extra keys)]: the file itself, or its kept components; smoothed last"""
+            if smooth_radius:
+                return [(smooth_rows(rows, smooth_radius, smooth_iters, keys["uid"], device=sample_device or "cuda"), keys) for rows, keys in split_of(cur_data, uid)]
+            return split_of(cur_data, uid)
+
+        def split_of(cur_data, uid):
             if not cluster_radius:
                 return [(cur_data, {"uid": uid})]
             rows = split_rows(cur_data, cluster_radius, cluster_min_points, cluster_mode, uid, device=sample_device or "cuda")
