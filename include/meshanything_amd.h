@@ -657,6 +657,51 @@ MA_API int    ma_op_pc_smooth(const float *ref, int N, int ref_ld, float radius,
                               void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_smooth_workspace_bytes(int N, int nx, int ny, int nz);
 
+/* ---- Upsampling of a sparse cloud: lattice points in every row's plane, kept where the row is the nearest, for --upsample_radius
+ * (csrc/pc_upsample.hpp); PCL's MovingLeastSquares::SAMPLE_LOCAL_PLANE upsampling with a Voronoi restriction.  Has no reference
+ * counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays
+ * (origin, dims, total and pair_bound are HOST pointers), caller-owned workspace.  NOT asynchronous: the call reads the pair bound and
+ * then the total back on `stream`, as ma_op_marching_cubes reads its counts.
+ *
+ * ma_op_pc_upsample: ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld >= 3; normals (N, 3) float64, a unit normal per row,
+ *   an INPUT (ma_op_pc_smooth fits one); active (N) bytes or NULL; m in 1..MA_PC_UPSAMPLE_MAX_M; step float64, the lattice spacing (pass
+ *   radius / m computed in float64).  Seed row i at position q is skipped when active is given and 0, when q is not finite or when its
+ *   normal n is not finite.  All of the following is float64 with no FMA contraction, IEEE division and square root.
+ *   Frame: a = the axis with the smallest |n_a|, ties to the lowest axis; u0 = e_a - n_a * n, each component as written; u = u0 /
+ *   sqrt((u0x*u0x + u0y*u0y) + u0z*u0z); v = n x u, v_x = n_y*u_z - n_z*u_y and cyclically, NOT renormalised.
+ *   Candidates: for a in -m..m (outer loop) and b in -m..m (inner loop), (a, b) != (0, 0), integer a*a + b*b <= m*m: da = (double)a * step,
+ *   db = (double)b * step, p_x = (double)q_x + (da*u_x + db*v_x), likewise y and z; c = (float)p, round to nearest.  A non-finite c is dropped.
+ *   Keep test, a Voronoi restriction: c is kept iff seed i comes first among ALL rows j in the order (d, index),
+ *       d = fl32(fl32(dx * dx + dy * dy) + dz * dz),  dx = fl32(c_x - x_j), dy = fl32(c_y - y_j), dz = fl32(c_z - z_j)
+ *   (the key of ma_op_pc_knn, no FMA contraction; a NaN key counts as +inf).  A candidate nearer to another row belongs to that row's patch
+ *   or to nobody, duplicated rows give all their candidates to the lower index, and the patches of neighbouring seeds do not overlap.
+ *   Output: the kept candidates seed-major, within a seed in (a, b) loop order: out_xyz (T, 3) fp32, out_seed (T) int32 the seed of each,
+ *   counts (N) int32 the kept candidates per seed (or NULL), *total = T.  The decision and the bits are a function of the inputs alone --
+ *   not of the grid, of the order of the records inside a cell, or of the run; nothing is accumulated -- so a numpy restatement that
+ *   evaluates the keys against all rows gives EQUAL outputs.
+ *   out_xyz = NULL (then out_seed = NULL too): count only; counts and *total are written, whatever the total.  Otherwise a total above
+ *   MA_PC_GRID_MAX_POINTS - N, or above `capacity` (the rows out_xyz and out_seed hold), fails with MA_ERR_INVALID with *total set, and
+ *   nothing is written to counts, out_xyz or out_seed.
+ *   Consequences of the rule, not defects: the patches are flat; an open border grows outward by up to the radius m * step; at a sharp
+ *   edge the fitted plane is diagonal and the patch sticks out; choose the radius at about one to two point spacings.
+ *   The grid (origin, cell, dims: as for ma_op_pc_knn_grid, the same faces and cell rule) only decides the time.  A candidate's block of
+ *   cells grows ring by ring from its own cell; it ends as not kept at the first row that precedes the seed, and as kept when the block
+ *   is the whole grid or fl32(b * b) > the seed's key, strictly, for the distance b = fl32(c - face) to every side of the block that is
+ *   not a grid border.  The pair bound is ma_op_pc_cluster's with radius fl32(m * step): computed before the long kernels, written to
+ *   *pair_bound (if given), and above max_pairs (0 = MA_PC_CLUSTER_MAX_PAIRS) the call fails with MA_ERR_INVALID and launches nothing
+ *   further; a grid whose float32 faces would break the bound is refused before any device work.
+ *   Non-finite coordinates or normals: such a row seeds nothing; nothing is read or written out of bounds.
+ *   1 <= N <= MA_PC_GRID_MAX_POINTS, N * (2m+1)^2 <= 2^31, step finite and > 0, the grid limits of ma_op_pc_knn_grid, m * step / cell <= 8.
+ *   workspace: ma_pc_upsample_workspace_bytes(N, nx, ny, nz) bytes of device memory (0 for arguments outside those limits): the grid's
+ *   layout, the 8-byte pair total, N + 1 64-bit offsets and their scan's tiles; its contents on entry do not matter. */
+#define MA_PC_UPSAMPLE_MAX_M 64
+MA_API int    ma_op_pc_upsample(const float *ref, int N, int ref_ld, const double *normals, const uint8_t *active /* or NULL */,
+                                int m, double step, const float *origin, float cell, const int32_t *dims, uint64_t max_pairs,
+                                int32_t *counts /* or NULL */, float *out_xyz /* or NULL: count only */, int32_t *out_seed /* or NULL */,
+                                uint64_t capacity, uint64_t *total /* host */, uint64_t *pair_bound /* host */,
+                                void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_upsample_workspace_bytes(int N, int nx, int ny, int nz);
+
 /* ---- Dominant planes: RANSAC hypothesis scoring and one plane applied, for --plane_threshold (csrc/pc_plane.hpp).  Has no reference
  * counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays
  * (`plane` is a HOST array of six floats), caller-owned workspace, asynchronous on `stream`.

@@ -43,6 +43,15 @@ cleaning steps and once per kept part: every point is projected onto the plane f
 pc_normal file's normals are replaced by the fitted ones on the file's side; sampling and the pc_xyz normal estimate then see the smoothed
 points, and one line per input reports how far they moved.  It removes measurement noise on the surface itself, which no other step touches.
 A plane fit shrinks a curved surface by roughly R^2 / (8 * its radius of curvature) and rounds edges over a width of R.
+`--upsample_radius R` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) then upsamples a SPARSE input, once
+per kept part and before sampling: an input of fewer than `--upsample_points` points (default 16384, 4096..4194304) gains lattice points
+at spacing R / m in the plane fitted to the points within R of each point, each kept where its own point is the nearest, on the GPU over
+the same cell grid (`meshanything_amd/pc_upsample.py`); m is the first of 2, 4, ..., 64 that reaches `--upsample_points`.  A new row copies
+its seed's row, so a pc_normal file's normals are the seed's; the pc_xyz normal estimate sees the upsampled points; one line per input
+reports m and the rows before and after.  With it an input file, the survivors of the cleaning steps and `--cluster_min_points` may go down
+to 64 points instead of 4096.  The patches are flat, an open border grows outward by up to R, and at a sharp edge the fitted plane is
+diagonal and the patch sticks out: choose R at about one to two point spacings, and use `--point_sampling fps`, since a uniform draw
+follows the uneven density that patches of different size leave.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -109,7 +118,23 @@ def get_args(argv=None):
                    help="with --input_type pc_normal / pc_xyz: smooth the input last of the cleaning steps: project every point onto the plane fitted to "
                         "the points within this distance of it, in the units of the input file (0 = off)")
     p.add_argument("--smooth_iters", default=None, type=int, help="with --smooth_radius: smoothing passes (1..8, default 1)")
+    p.add_argument("--upsample_radius", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: upsample a sparse input after the cleaning steps: add lattice points in the plane fitted to "
+                        "the points within this distance of each point, in the units of the input file, each kept where its own point is the nearest "
+                        "(0 = off).  The patches are flat, an open border grows outward by up to this distance, and at a sharp edge the patch sticks "
+                        "out: choose about one to two point spacings, and use --point_sampling fps, which thins the uneven density evenly")
+    p.add_argument("--upsample_points", default=None, type=int,
+                   help="with --upsample_radius: upsample an input of fewer points to at least this many (4096..4194304, default 16384 = 4 x 4096)")
     args = p.parse_args(argv)
+    if not (0.0 <= args.upsample_radius < float("inf")):
+        p.error("--upsample_radius must be finite and >= 0 (0 = off)")
+    if args.input_type == "mesh" and (args.upsample_radius != 0 or args.upsample_points is not None):
+        p.error("--upsample_radius and --upsample_points apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+    if args.upsample_radius == 0 and args.upsample_points is not None:
+        p.error("--upsample_points needs --upsample_radius > 0")
+    if args.upsample_points is not None and not 4096 <= args.upsample_points <= 1 << 22:
+        p.error("--upsample_points must be in 4096..4194304")
+    args.upsample_points = 4 * 4096 if args.upsample_points is None else args.upsample_points
     if not (0.0 <= args.smooth_radius < float("inf")):
         p.error("--smooth_radius must be finite and >= 0 (0 = off)")
     if args.input_type == "mesh" and (args.smooth_radius != 0 or args.smooth_iters is not None):
@@ -141,7 +166,9 @@ def get_args(argv=None):
         p.error("--cluster_radius, --cluster_mode and --cluster_min_points apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
     if args.cluster_radius == 0 and (args.cluster_mode is not None or args.cluster_min_points is not None):
         p.error("--cluster_mode and --cluster_min_points need --cluster_radius > 0")
-    if args.cluster_min_points is not None and args.cluster_min_points < 4096:
+    if args.cluster_min_points is not None and args.upsample_radius > 0 and args.cluster_min_points < 64:
+        p.error("--cluster_min_points must be at least 64, the rows upsampling takes")
+    if args.cluster_min_points is not None and args.upsample_radius == 0 and args.cluster_min_points < 4096:
         p.error("--cluster_min_points must be at least 4096, the rows the uniform draw needs")
     args.cluster_mode = args.cluster_mode or "largest"
     args.cluster_min_points = 4096 if args.cluster_min_points is None else args.cluster_min_points
@@ -216,7 +243,8 @@ def main():
                           outlier_k=args.outlier_k, outlier_std=args.outlier_std, cluster_radius=args.cluster_radius, cluster_mode=args.cluster_mode,
                           cluster_min_points=args.cluster_min_points, plane_threshold=args.plane_threshold, plane_iters=args.plane_iters,
                           plane_count=args.plane_count, plane_min_fraction=args.plane_min_fraction, smooth_radius=args.smooth_radius,
-                          smooth_iters=args.smooth_iters)
+                          smooth_iters=args.smooth_iters, upsample_radius=args.upsample_radius,
+                          upsample_points=args.upsample_points if args.upsample_radius > 0 else None)
 
     begin = time.time()
     print("Generation Start!!!")

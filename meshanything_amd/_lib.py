@@ -140,6 +140,9 @@ SIGNATURES = {
     "ma_pc_cluster_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "ma_op_pc_smooth": (_I, [_P, _I, _I, _F, _P, _F, _P, _I, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint64), _P, C.c_size_t, _P]),
     "ma_pc_smooth_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "ma_op_pc_upsample": (_I, [_P, _I, _I, _P, _P, _I, C.c_double, _P, _F, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint64), _P, C.c_size_t, _P]),
+    "ma_pc_upsample_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "ma_op_pc_plane_score": (_I, [_P, _I, _I, _P, _I, _F, _P, _P, _P, _P, C.c_size_t, _P]),
     "ma_op_pc_plane_apply": (_I, [_P, _I, _I, _P, _F, _P, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_plane_workspace_bytes": (C.c_size_t, [_I, _I]),

@@ -46,6 +46,7 @@
 #include "pc_grid.hpp"
 #include "pc_cluster.hpp"
 #include "pc_smooth.hpp"
+#include "pc_upsample.hpp"
 #include "pc_plane.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
@@ -1206,6 +1207,63 @@ int ma_op_pc_smooth(const float* ref, int N, int ref_ld, float radius, const flo
             throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
                                               ": use a smaller radius or fewer points");
         HIP_CHECK(pcs::launch_smooth(N, r2, g, min_count, moved, normals, eigvals, count, workspace, s));
+    });
+}
+
+// ---- upsampling: lattice points in every row's plane, kept where the row is the nearest (csrc/pc_upsample.hpp) ------------------------------
+static_assert(MA_PC_UPSAMPLE_MAX_M == pcu::MAX_M, "the header's limit is the kernels'");
+size_t ma_pc_upsample_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcu::layout(N, nx * ny * nz).bytes : 0; }
+
+int ma_op_pc_upsample(const float* ref, int N, int ref_ld, const double* normals, const uint8_t* active, int m, double step, const float* origin, float cell,
+                      const int32_t* dims, uint64_t max_pairs, int32_t* counts, float* out_xyz, int32_t* out_seed, uint64_t capacity, uint64_t* total,
+                      uint64_t* pair_bound, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !normals || !origin || !dims || !total || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: null pointer");
+        if (!out_xyz && out_seed) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: out_seed without out_xyz: a count-only call takes neither");
+        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        if (ref_ld < 3) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: ref_ld must be at least 3");
+        if (m < 1 || m > pcu::MAX_M) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: m must be in 1..64");
+        if ((int64_t)N * (2 * m + 1) * (2 * m + 1) > pcu::MAX_SLOTS)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: N * (2m+1)^2 must be at most 2^31");
+        volatile float radius = (float)((double)m * step);
+        if (!std::isfinite(step) || !(step > 0.0) || !std::isfinite(radius) || !(radius > 0.f))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: step must be finite and > 0, and m * step a positive finite float32");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: origin must be finite");
+        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: cell must be finite and > 0");
+        if (!((double)m * step / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: m * step / cell must be at most 8");
+        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
+        volatile float r2 = radius * radius;
+        const int R = pcc::rings(radius, cell);
+        if (!pcc::rings_suffice(g, r2, R))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the float32 faces of this grid do not separate cells " + std::to_string(R) +
+                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
+        if (workspace_bytes < pcu::layout(N, pcg::cells_of(g)).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: workspace smaller than ma_pc_upsample_workspace_bytes(N, nx, ny, nz)");
+        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        *total = 0;
+        HIP_CHECK(pcu::launch_bound(ref, N, ref_ld, g, R, workspace, s));
+        unsigned long long bound = 0;
+        HIP_CHECK(hipMemcpyAsync(&bound, pcu::total_of(N, g, workspace), sizeof(bound), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (pair_bound) *pair_bound = bound;
+        if (bound > cap)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the pair bound " + std::to_string(bound) + " exceeds max_pairs " + std::to_string(cap) +
+                                              ": use a smaller radius or fewer points");
+        HIP_CHECK(pcu::launch_count(ref, N, ref_ld, normals, active, m, step, g, out_xyz ? nullptr : counts, workspace, s));
+        long long kept = 0;
+        HIP_CHECK(hipMemcpyAsync(&kept, pcu::offs_of(N, g, workspace) + N, sizeof(kept), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        *total = (uint64_t)kept;
+        if (!out_xyz) return;                                       // count only
+        if ((uint64_t)kept > (uint64_t)MA_PC_GRID_MAX_POINTS - (uint64_t)N)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the total " + std::to_string(kept) + " exceeds 2^22 - N = " +
+                                              std::to_string(MA_PC_GRID_MAX_POINTS - N) + ": use a smaller m or radius");
+        if ((uint64_t)kept > capacity)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the total " + std::to_string(kept) + " exceeds the capacity " + std::to_string(capacity) +
+                                              " of out_xyz / out_seed: nothing was written");
+        HIP_CHECK(pcu::launch_emit(ref, N, ref_ld, normals, active, m, step, g, counts, out_xyz, out_seed, (int64_t)capacity, workspace, s));
     });
 }
 

@@ -84,17 +84,39 @@ class Dataset:
     replaced by the fitted ones on the file's side.  The strays and the table are gone by then and cannot pull the fit.  The uniform draw
     or FPS then runs over the smoothed rows, and pc_xyz estimates its normals from them.  A plane fit shrinks a curved surface by roughly
     R^2 / (8 * its radius of curvature) and rounds edges over a width of R.  0 = off: no code path, key, print or RNG draw changes.
-    With "mesh" a non-zero value is a ValueError."""
+    With "mesh" a non-zero value is a ValueError.
+
+    upsample_radius=R > 0 (pc_normal and pc_xyz; the reference has nothing like it): upsampling of a SPARSE cloud, after smoothing and once
+    per kept part, before the uniform draw, FPS or the pc_xyz normal estimate (pc_upsample.upsample_rows on the GPU): a part of fewer than
+    upsample_points rows (default 4 * n_points, n_points..2^22) gains lattice points at spacing R / m in the plane fitted to the rows within
+    R of each row (file units), each kept where its own row is the nearest, m the first of 2, 4, ..., 64 that reaches upsample_points; a new
+    row is a copy of its seed's row with xyz replaced, so a file's normals are the seed's, and pc_xyz estimates its normals from the
+    upsampled rows.  With it, and only then, the floor on the rows of a file, of the outlier filter's and plane removal's survivors and of
+    cluster_min_points is pc_upsample.MIN_ROWS = 64 instead of n_points; fewer than n_points rows after upsampling is a ValueError.  The
+    patches are flat, an open border grows outward by up to R, at a sharp edge the patch sticks out; choose R at about one to two point
+    spacings, and prefer point_sampling="fps": a uniform draw follows the uneven density that patches of different size leave.  0 = off: no
+    code path, key, print, floor or RNG draw changes.  With "mesh" a non-zero value is a ValueError."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
                  cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
-                 plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1):
+                 plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1,
+                 upsample_radius: float = 0.0, upsample_points=None):
         self.data: List[Dict] = []
         if point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {point_sampling!r}')
         if point_sampling == "fps" and input_type == "mesh":
             raise ValueError('point_sampling="fps" applies to pc_normal and pc_xyz inputs: the points of a mesh input are already drawn from its surface')
+        floor = n_points                                             # the fewest rows a file, and what a cleaning step leaves of it, may have
+        if upsample_radius:
+            from .pc_upsample import MIN_ROWS, check_upsample_args, upsample_rows
+            if input_type == "mesh":
+                raise ValueError("upsample_radius applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
+            upsample_points = 4 * n_points if upsample_points is None else upsample_points
+            check_upsample_args(upsample_radius, upsample_points, n_points)   # before any file is read
+            floor = min(MIN_ROWS, n_points)
+        elif upsample_points is not None:
+            raise ValueError("upsample_points needs upsample_radius > 0")
         if outlier_k:
             from .pc_outliers import check_filter_args, filter_rows
             if input_type == "mesh":
@@ -110,8 +132,9 @@ class Dataset:
             if input_type == "mesh":
                 raise ValueError("cluster_radius applies to pc_normal and pc_xyz inputs: the points of a mesh input are drawn from its surface")
             check_split_args(cluster_radius, cluster_min_points, cluster_mode)
-            if cluster_min_points < n_points:
-                raise ValueError(f"cluster_min_points = {cluster_min_points} is less than the {n_points} rows the encoder takes")
+            if cluster_min_points < floor:
+                raise ValueError(f"cluster_min_points = {cluster_min_points} is less than the {floor} rows " +
+                                 ("upsampling takes" if upsample_radius else "the encoder takes"))
         if smooth_radius:
             from .pc_smooth import check_smooth_args, smooth_rows
             if input_type == "mesh":
@@ -119,7 +142,20 @@ class Dataset:
             check_smooth_args(smooth_radius, smooth_iters)           # before any file is read
 
         def parts_of(cur_data, uid):
-            """[(rows of the file that stand in for it, the item's extra keys)]: the file itself, or its kept components; smoothed last"""
+            """[(rows of the file that stand in for it, the item's extra keys)]: the file itself, or its kept components; smoothed, then upsampled"""
+            if not upsample_radius:
+                return smoothed_of(cur_data, uid)
+            parts = []
+            for rows, keys in smoothed_of(cur_data, uid):
+                if rows.shape[0] < floor:
+                    raise ValueError(f"{keys['uid']}: upsampling takes at least {floor} rows, got {rows.shape[0]}")
+                rows = upsample_rows(rows, upsample_radius, upsample_points, keys["uid"], device=sample_device or "cuda")
+                if rows.shape[0] < n_points:
+                    raise ValueError(f"{keys['uid']}: upsampling left {rows.shape[0]} rows, fewer than the {n_points} the encoder takes")
+                parts.append((rows, keys))
+            return parts
+
+        def smoothed_of(cur_data, uid):
             if smooth_radius:
                 return [(smooth_rows(rows, smooth_radius, smooth_iters, keys["uid"], device=sample_device or "cuda"), keys) for rows, keys in split_of(cur_data, uid)]
             return split_of(cur_data, uid)
@@ -135,9 +171,9 @@ class Dataset:
             for input_path in input_list:
                 cur_data = np.load(input_path)
                 if outlier_k:
-                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
+                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, floor, uid_of(input_path), device=sample_device or "cuda")
                 if plane_threshold:
-                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, n_points, uid_of(input_path),
+                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, floor, uid_of(input_path),
                                                       device=sample_device or "cuda")]
                 for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
                     if point_sampling == "fps":
@@ -161,11 +197,11 @@ class Dataset:
             from .pc_normals import check_xyz, xyz_to_pc_normal
             for input_path in input_list:
                 cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
-                cur_data = check_xyz(cur_data, n_points, normal_k)       # shape, length, finite: before anything touches the GPU
+                cur_data = check_xyz(cur_data, floor, normal_k)          # shape, length, finite: before anything touches the GPU
                 if outlier_k:
-                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, n_points, uid_of(input_path), device=sample_device or "cuda")
+                    cur_data = filter_rows(cur_data, outlier_k, outlier_std, floor, uid_of(input_path), device=sample_device or "cuda")
                 if plane_threshold:
-                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, n_points, uid_of(input_path),
+                    cur_data = cur_data[remove_planes(cur_data, plane_threshold, plane_iters, plane_count, plane_min_fraction, floor, uid_of(input_path),
                                                       device=sample_device or "cuda")]
                 for cur_data, keys in parts_of(cur_data, uid_of(input_path)):
                     self.data.append({"pc_normal": xyz_to_pc_normal(cur_data, n_points, normal_k, device=sample_device or "cuda", sampling=point_sampling), **keys})
