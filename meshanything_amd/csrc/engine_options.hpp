@@ -76,7 +76,7 @@ const Opt OPTIONS[] = {
     {.name = "fuse_oproj_fc1", .field = &Options::fuse_oproj_fc1, .get = [](ma_engine* e) -> int64_t { return fuse_oproj_fc1(e) ? 1 : 0; }, .flag = true, .effects = DROPS_GRAPHS},
     {.name = "fuse_fc2", .field = &Options::fuse_fc2, .effects = DROPS_GRAPHS},
     {.name = "qkv_xcd_local", .field = &Options::qkv_xcd_local, .flag = true, .effects = DROPS_GRAPHS},
-    {.name = "oproj_fc1_sweep_waves", .field = &Options::oproj_fc1_sweep_waves, .effects = DROPS_GRAPHS},
+    {.name = "oproj_fc1_sweep_waves", .field = &Options::oproj_fc1_sweep_waves, .ok = one_of(1, 2, 4), .bad = "oproj_fc1_sweep_waves must be 1, 2 or 4", .effects = DROPS_GRAPHS},
     // (read back as the engine will apply it at profile_batch rows: the matrix-core batches keep their embedding launch)
     {.name = "embed_table", .field = &Options::embed_table, .get = [](ma_engine* e) -> int64_t { return embed_from_table(e, std::max(1, std::min(e->opt.profile_batch, e->cfg.max_batch))) ? 1 : 0; },
      .flag = true, .effects = DROPS_GRAPHS},

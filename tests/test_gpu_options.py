@@ -7,6 +7,7 @@ import torch
 from meshanything_amd._lib import MAError
 from meshanything_amd.config import MAConfig, DTYPE_BF16
 from conftest import cached_state_dict, load_weights_cached, mouse_variants
+from test_gpu_pipeline import GREEDY_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +16,7 @@ NEEDS_EXP = " needs a library built with MA_EXPERIMENTAL=1 (the rejected decode-
 
 # name: (default, values stored as given)                      -- no range check
 PLAIN = {"mfma_min_batch": (4, (1, 65, 4)), "attn_final_min_batch": (8, (0, 12, 8)), "attn_rowwave": (1, (0, 1)), "mfma_fold_ln": (1, (0, 1)),
-         "attn_pair": (1, (0, 1)), "mfma_fold_fc1_max": (8, (0, 16, 8)), "mfma_fold_qkv_max": (8, (0, 16, 8)), "oproj_fc1_sweep_waves": (4, (1, 2, 4)),
+         "attn_pair": (1, (0, 1)), "mfma_fold_fc1_max": (8, (0, 16, 8)), "mfma_fold_qkv_max": (8, (0, 16, 8)),
          "fuse_fc2": (1, (0, 1)), "rows_fused_min": (4, (2, 8, 4)), "gemm_xcd_swizzle": (1, (0, 1)), "use_graph": (1, (0, 1))}
 # name: (default, accepted values, one refused value on each side, message)      -- a documented list or range; the last accepted value is the default
 LISTED = {"mfma_fc2_ksplit": (0, (1, 2, 0), (-1, 3), "mfma_fc2_ksplit must be 0 (default), 1, 2 or 4"),
@@ -29,7 +30,8 @@ LISTED = {"mfma_fc2_ksplit": (0, (1, 2, 0), (-1, 3), "mfma_fc2_ksplit must be 0 
           "attn_impl": (2, (1, 2), (0, 3), "attn_impl: 1 (attn.hpp) or 2 (attn2.hpp)"),
           "gemv_rpw": (4, (1, 2, 4), (0, 3), "gemv_rpw must be 1, 2 or 4"),
           "gemv_small_rows": (1, (0, 2, 4, 1), (-1, 3), "gemv_small_rows must be 0, 1, 2 or 4"),
-          "gemv_k8_ksplit": (1, (2, 4, 1), (0, 3), "gemv_k8_ksplit must be 1, 2 or 4")}
+          "gemv_k8_ksplit": (1, (2, 4, 1), (0, 3), "gemv_k8_ksplit must be 1, 2 or 4"),
+          "oproj_fc1_sweep_waves": (4, (1, 2, 4), (0, 5), "oproj_fc1_sweep_waves must be 1, 2 or 4")}
 # can be set, and the parent cannot read them back (a library that can returns the stored value): name: (accepted, refused, message)
 WRITE_ONLY = {"gemm_impl": ((1, 0), (), ""), "prefill_stepwise": ((1, 0), (), ""), "profile_batch": ((8, 1), (), "")}
 # stored as value != 0, read back as stored
@@ -75,6 +77,27 @@ def _unknown(eng, call, name):
     with pytest.raises(MAError) as ei:
         call()
     assert ei.value.code == INVALID and ("unknown option " + name) in str(ei.value), (name, str(ei.value))
+
+
+def _decisive(logits, tol):
+    """(rows, steps) bool: the steps at which the run's own top-1 / top-2 logit margin (eos suppressed) exceeds 2 x tol."""
+    lg = logits.clone()
+    lg[:, :, 1] = float("-inf")
+    top2 = torch.topk(lg, 2, dim=-1).values
+    return ((top2[..., 0] - top2[..., 1]) > 2 * tol).cpu()
+
+
+def _agrees_where_decisive(eng, prefix, want, decisive, what, **kw):
+    """A form that orders a sum differently (same_there=False below) may leave the default's stream at a near-tie, so its free-running tokens are only
+    checked for their shape; its NUMBERS are held to the reference's logits in tests/test_gpu_step_forms.py.  Here: walked along the default run's
+    stream (teacher forcing, so that every step has the default's context), its own pick is the default's at every step where the default run's
+    margin is decisive."""
+    picks, _ = eng.generate(prefix, suppress_eos=True, forced_tokens=want, **kw)
+    picks = picks.cpu()
+    assert picks.shape == want.shape and bool(decisive.any()), what
+    bad = (picks != want) & decisive
+    print(f"[options] {what}: {int(decisive.sum())} of {decisive.numel()} steps decisive, picks differ from the default's at {int((picks != want).sum())} steps")
+    assert not bool(bad.any()), (what, "picks differ from the default's at decisive steps (row, step)", bad.nonzero().tolist()[:8])
 
 
 def test_defaults_values_and_refusals(tiny):
@@ -225,6 +248,9 @@ def test_setters_drop_the_captured_steps(tiny):
             want, want_len = eng.generate(p, suppress_eos=True)
             want = want.cpu()
             assert want.shape == (rows, cfg.max_new_tokens)
+            again, _, want_lg = eng.generate(p, suppress_eos=True, return_logits=True)
+            assert torch.equal(again.cpu(), want)
+            decisive = _decisive(want_lg, GREEDY_TOL["bf16"])
 
             def same(what):
                 got, got_len = eng.generate(p, suppress_eos=True)
@@ -239,6 +265,7 @@ def test_setters_drop_the_captured_steps(tiny):
                 else:
                     got, _ = eng.generate(p, suppress_eos=True)
                     assert got.shape == want.shape
+                    _agrees_where_decisive(eng, p, want, decisive, (rows, f"{name}={there}"))
                 eng.set_option(name, back)
                 same(f"{name} back to {back}")
         # The sharp check that the graphs ARE dropped: 6 rows step on the matrix cores; with mfma_min_batch = 65 they step on the GEMV chain (another
@@ -269,10 +296,15 @@ def test_gemv_rpw_recaptures_the_step_at_the_350m_shape(full8, golden_dir):
     want, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
     want = want.cpu()
     assert len(set(want[0].tolist())) > 8
+    again, _, want_lg = eng.generate(prefix, max_new_tokens=96, suppress_eos=True, return_logits=True)
+    assert torch.equal(again.cpu(), want)
+    decisive = _decisive(want_lg, GREEDY_TOL["bf16"])
     for name, there, back, same_there in (("gemv_rpw", 2, 4, True), ("gemv_rpw", 1, 4, True), ("gemv_small_rows", 2, 1, False), ("gemv_k8_ksplit", 2, 1, False)):
         eng.set_option(name, there)
         got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
         assert got.shape == want.shape and (not same_there or torch.equal(got.cpu(), want)), (name, there)
+        if not same_there:
+            _agrees_where_decisive(eng, prefix, want, decisive, f"{name}={there}", max_new_tokens=96)
         eng.set_option(name, back)
         got, _ = eng.generate(prefix, max_new_tokens=96, suppress_eos=True)
         assert torch.equal(got.cpu(), want), (name, "back to", back)
