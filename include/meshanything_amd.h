@@ -354,6 +354,33 @@ MA_API int  ma_op_ln_rows(const float *x, int ldx, int xin_grp, int xin_gstride,
                           float *y32, int ld32, void *act, int lda, int act_dtype, int yout_grp, int yout_gstride, int yout_off,
                           int rows, int D, int parts, int64_t part_stride, int split_rows, void *stream);
 
+/* ---- test aid: dense attention as the dense phases launch it (Dense::attention, csrc/engine_dense.hpp): a batch of samples along grid.z with element
+ * strides between the samples, a shortened last sample, the caller's V^T workspace -- csrc/attn.hpp launch_attention and csrc/attn2.hpp
+ * launch_attention2 themselves, not a copy of their logic.  Has no reference counterpart (the reference calls attention on whole (B, S, heads, 64)
+ * tensors).  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first launch (MA_ERR_INVALID), what the launchers
+ * refuse comes back as MA_ERR_INVALID as well; all arrays are device memory, 16-byte aligned.  Does not synchronise `stream`.
+ *   O[b * o_bs + q * o_rs + h * 64 + d] = softmax(Q K^T * scale) V of sample b and head h, head_dim 64;
+ *   X[b * x_bs + row * x_rs + h * x_hs + d] for X = Q, K, V: all strides in elements, >= 0 (q_bs == 0: one Q for every sample), row strides >= 64.
+ *   kernel 0: the fp32 kernel on fp32 tensors (strides multiples of 4) | 3: the first-generation matrix-core kernel on 16-bit tensors (bf16 only,
+ *     strides multiples of 8) | 4: csrc/attn2.hpp on 16-bit tensors in the format of ma_op_set_half_dtype (strides multiples of 8).
+ *   causal_offset < 0: every key visible; else query i sees keys <= causal_offset + i.
+ *   last_len > 0 (kernel 4 only; < 0: none): the LAST sample has Sq = Sk = last_len <= min(Sq, Sk) rows; what its tensors hold behind them is neither
+ *     read nor written.
+ *   vt / vt_elems (kernel 4): the V^T workspace of at least ma_attention_vt_workspace_elems(Sk, H, batch) 16-bit elements. */
+typedef struct ma_attn_dense_args {
+    int32_t struct_size;                 /* = sizeof(ma_attn_dense_args) */
+    int32_t kernel;
+    int32_t Sq, Sk, H, causal_offset, batch, last_len;
+    float scale;
+    int32_t q_rs, q_hs, k_rs, k_hs, v_rs, v_hs, o_rs;
+    uint64_t q_bs, k_bs, v_bs, o_bs;     /* elements */
+    uint64_t vt_elems;
+    const void *Q, *K, *V;
+    void *O, *vt;
+} ma_attn_dense_args;
+MA_API int  ma_op_attention_dense(ma_attn_dense_args *args, void *stream);
+MA_API size_t ma_attention_vt_workspace_elems(int Sk, int H, int batch);
+
 /* ---- measurement aid: dst[0, bytes) = src[0, bytes) as a 16-byte-per-lane streaming copy; bytes % 16 == 0; mode 0 = 2048 blocks grid-stride with
  * non-temporal accesses, 1 = one element per thread with plain accesses, 2 = one element per thread non-temporal.  bench.py times all three and
  * reports the box's achievable HBM rate next to the 8 TB/s vendor number.  No reference counterpart. */

@@ -60,6 +60,18 @@ class GemmDenseArgs(C.Structure):
         self.struct_size = C.sizeof(GemmDenseArgs)
 
 
+class AttnDenseArgs(C.Structure):
+    """ma_attn_dense_args (test aid ma_op_attention_dense): struct_size is filled in here."""
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "kernel", "Sq", "Sk", "H", "causal_offset", "batch", "last_len")] + [("scale", C.c_float)] +
+                [(n, C.c_int32) for n in ("q_rs", "q_hs", "k_rs", "k_hs", "v_rs", "v_hs", "o_rs")] +
+                [(n, C.c_uint64) for n in ("q_bs", "k_bs", "v_bs", "o_bs", "vt_elems")] +
+                [(n, C.c_void_p) for n in ("Q", "K", "V", "O", "vt")])
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(AttnDenseArgs)
+
+
 # every symbol include/meshanything_amd.h declares: name -> (restype, argtypes)
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -111,6 +123,8 @@ SIGNATURES = {
     "ma_op_set_half_dtype": (_I, [_I]),
     "ma_op_gemm_dense": (_I, [C.POINTER(GemmDenseArgs), _P]),
     "ma_op_ln_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_int64, _I, _P]),
+    "ma_op_attention_dense": (_I, [C.POINTER(AttnDenseArgs), _P]),
+    "ma_attention_vt_workspace_elems": (C.c_size_t, [_I, _I, _I]),
     "ma_engine_persist_available": (_I, [_P]),
     "ma_persist_trace": (_I, [_P, _I, _P, C.POINTER(C.c_int32), _P]),
     "ma_engine_read_logits": (_I, [_P, _I, _P, _P]),

@@ -317,10 +317,13 @@ inline hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     if (a.Sq <= 0) return hipSuccess;
     if (a.last_len >= 0) return hipErrorInvalidValue;       // (attn2.hpp only)
     if (a.round_bf16 == 1) hipLaunchKernelGGL(attention_mfma_kernel<float>, dim3((a.Sq + 63) / 64, a.H, a.batch), dim3(256), 0, s, a);
-    else if (a.round_bf16 == 3) hipLaunchKernelGGL(attention_mfma_kernel<bf16_t>, dim3((a.Sq + 63) / 64, a.H, a.batch), dim3(256), 0, s, a);
-    else {
+    else if (a.round_bf16 == 3) {
+        // 16-byte loads of eight bf16: every input stride a multiple of 8 elements
+        if ((a.q_rs | a.k_rs | a.v_rs | a.q_hs | a.k_hs | a.v_hs) % 8 || (a.q_bs | a.k_bs | a.v_bs) % 8) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(attention_mfma_kernel<bf16_t>, dim3((a.Sq + 63) / 64, a.H, a.batch), dim3(256), 0, s, a);
+    } else {
         // 16-byte row accesses: every stride a multiple of 4 elements.  96-row blocks when they waste fewer rows than 128-row ones (257 rows)
-        if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs) % 4) return hipErrorInvalidValue;
+        if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs) % 4 || (a.q_bs | a.k_bs | a.v_bs | a.o_bs) % 4) return hipErrorInvalidValue;
         const int pad3 = (a.Sq + 95) / 96 * 96, pad4 = (a.Sq + 127) / 128 * 128;
         if (pad3 < pad4) hipLaunchKernelGGL(attention_f32_kernel<3>, dim3(pad3 / 96, a.H, a.batch), dim3(192), 0, s, a);
         else hipLaunchKernelGGL(attention_f32_kernel<4>, dim3(pad4 / 128, a.H, a.batch), dim3(256), 0, s, a);

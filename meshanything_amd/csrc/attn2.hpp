@@ -277,7 +277,7 @@ inline hipError_t launch_attention2(const AttnArgs& a, bf16_t* vt, hipStream_t s
     const int skp = (a.Sk + 63) & ~63;
     if (a.last_len == 0 || a.last_len > a.Sq || a.last_len > a.Sk) return hipErrorInvalidValue;
     const int Sq_last = a.last_len > 0 ? a.last_len : a.Sq, Sk_last = a.last_len > 0 ? a.last_len : a.Sk;
-    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs) % 8) return hipErrorInvalidValue;      // 16-byte vector accesses
+    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs) % 8 || (a.q_bs | a.k_bs | a.v_bs | a.o_bs) % 8) return hipErrorInvalidValue;      // 16-byte vector accesses
     hipLaunchKernelGGL(vt_pack_kernel, dim3(skp / 64, a.H, a.batch), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(a.V), a.v_rs, a.v_hs, a.v_bs, vt, a.Sk, skp, a.H, Sk_last);
     Attn2Args g{reinterpret_cast<const bf16_t*>(a.Q), a.q_rs, a.q_hs, reinterpret_cast<const bf16_t*>(a.K), a.k_rs, a.k_hs, vt, reinterpret_cast<bf16_t*>(a.O), a.o_rs,
                 a.Sq, a.Sk, skp, a.H, a.scale, a.causal_offset, a.q_bs, a.k_bs, a.o_bs, Sq_last, Sk_last};

@@ -583,6 +583,38 @@ int ma_op_attention(const float* Q, int q_rs, int q_hs, const float* K, int k_rs
     });
 }
 
+// test aid: launch_attention / launch_attention2 with everything Dense::attention can set
+int ma_op_attention_dense(ma_attn_dense_args* a, void* stream) {
+    return guarded(nullptr, [&] {
+        const std::string op = "ma_op_attention_dense";
+        if (!a) throw MaError(MA_ERR_INVALID, op + ": null arguments");
+        if (a->struct_size != (int32_t)sizeof(ma_attn_dense_args)) throw MaError(MA_ERR_INVALID, op + ": struct_size mismatch");
+        auto bad = [&](const char* what) { throw MaError(MA_ERR_INVALID, op + ": " + what); };
+        if (a->kernel != 0 && a->kernel != 3 && a->kernel != 4) bad("kernel must be 0 (fp32), 3 (first-generation MFMA, 16-bit tensors) or 4 (attn2)");
+        if (a->kernel == 3 && g_op_hdt != MA_DTYPE_BF16) bad("kernel 3 is bf16 only");
+        if (!a->Q || !a->K || !a->V || !a->O) bad("null pointer");
+        if (!aligned16(a->Q) || !aligned16(a->K) || !aligned16(a->V) || !aligned16(a->O) || !aligned16(a->vt)) bad("arrays must be 16-byte aligned");
+        if (a->Sq <= 0 || a->Sk <= 0 || a->H <= 0 || a->batch <= 0) bad("need Sq, Sk, H, batch > 0");
+        if (!(a->scale > 0.f) || !std::isfinite(a->scale)) bad("scale must be positive and finite");
+        if (a->Sq > (1 << 24) || a->Sk > (1 << 24) || a->causal_offset > (1 << 24)) bad("Sq, Sk and causal_offset must be at most 2^24");
+        if (a->q_rs < 64 || a->k_rs < 64 || a->v_rs < 64 || a->o_rs < 64 || a->q_hs < 0 || a->k_hs < 0 || a->v_hs < 0) bad("row strides must be >= 64, head strides >= 0");
+        if (a->H > 1 && (a->q_hs < 64 || a->k_hs < 64 || a->v_hs < 64 || a->o_rs < a->H * 64)) bad("more than one head needs head strides >= 64 and o_rs >= H * 64");
+        if (a->batch > 1 && (a->k_bs == 0 || a->v_bs == 0 || a->o_bs == 0)) bad("a batch needs sample strides for K, V and O (only q_bs may be 0)");
+        if ((a->q_bs | a->k_bs | a->v_bs | a->o_bs) >> 40) bad("sample strides must be below 2^40 elements");
+        if (a->kernel == 4) {
+            if (!a->vt) bad("kernel 4 needs the V^T workspace");
+            if (a->vt_elems < attn2_vt_elems(a->Sk, a->H, a->batch)) bad("V^T workspace too small (ma_attention_vt_workspace_elems)");
+        }
+        AttnArgs g{a->Q, a->q_rs, a->q_hs, a->K, a->k_rs, a->k_hs, a->V, a->v_rs, a->v_hs, a->O, a->o_rs, a->Sq, a->Sk, a->H, a->scale, a->causal_offset, a->kernel == 0 ? 0 : 3};
+        g.batch = a->batch; g.last_len = a->last_len; g.q_bs = (size_t)a->q_bs; g.k_bs = (size_t)a->k_bs; g.v_bs = (size_t)a->v_bs; g.o_bs = (size_t)a->o_bs;
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        if (a->kernel == 4) op_launched(H16_CALL(g_op_hdt, HT, launch_attention2<HT>(g, reinterpret_cast<bf16_t*>(a->vt), s)), "ma_op_attention_dense");
+        else op_launched(launch_attention(g, s), "ma_op_attention_dense");
+    });
+}
+
+size_t ma_attention_vt_workspace_elems(int Sk, int H, int batch) { return (Sk > 0 && H > 0 && batch > 0) ? attn2_vt_elems(Sk, H, batch) : 0; }
+
 int ma_op_decode_attention(int kvdtype, const float* q, const void* kcache, const void* vcache, int H, int max_seq, int len, float* out,
                            void* workspace, void* stream) {
     return guarded(nullptr, [&] {

@@ -25,7 +25,12 @@ Bound, per output element (bound()), derived from the arithmetic of ANY kernel t
                                    to that RELATIVE error, and a normalised mean of values within max|v| to twice it.  (Whether the errors of equal
                                    scores cancel between numerator and row sum depends on where a kernel rounds P; a bound may not assume it.)
 There is no P-rounding term: the top keys' p is 1 (exactly representable), the others are covered by the e^-30 term.  No element and no case is
-exempt."""
+exempt.
+
+Batched launches (stack(), Batch): the samples of one launch (grid.z) are Cases of one shape, every sample a pattern of its own, optionally followed by a
+shorter last sample (short_case) behind whose rows sits an adversarial key; the bound is per sample, unchanged.  layout_batch / last_len_batch / tail_batch
+build the launches of tests/test_gpu_attention_batched.py, wrong_variants() what four wrong kernels would compute for a sample."""
+import functools
 import math
 
 import numpy as np
@@ -89,15 +94,22 @@ def build(name, levels, signs, fmt, causal_offset=-1, twins=(), dims=None, seed=
     Sq = signs.shape[0]
     dims = [head_dim(h) for h in range(H)] if dims is None else list(dims)
     g = torch.Generator().manual_seed(int(seed))
-    k = torch.randn(Sk, H, 64, generator=g) + torch.linspace(-0.3, 0.3, 64)[None, None, :]
-    v = torch.randn(Sk, H, 64, generator=g) + torch.linspace(0.5, -0.5, 64)[None, None, :]
-    q = torch.zeros(Sq, H, 64)
-    hs = torch.arange(H)
-    d = torch.tensor(dims)
-    q[:, hs, d] = QMAG * signs.float()[:, None]
-    k[:, hs, d] = levels.float().t()
-    for (h, a, b) in twins:
-        k[b, h] = k[a, h]
+    # (host tensors of a few 10^4 elements, on ONE thread: above torch's parallel grain -- 257 keys x 2 heads x 64 -- every operation would wake the whole
+    #  pool, and a session may have left it wider than the cores this process may use: seconds per case on the GPU machine)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        k = torch.randn(Sk, H, 64, generator=g) + torch.linspace(-0.3, 0.3, 64)[None, None, :]
+        v = torch.randn(Sk, H, 64, generator=g) + torch.linspace(0.5, -0.5, 64)[None, None, :]
+        q = torch.zeros(Sq, H, 64)
+        hs = torch.arange(H)
+        d = torch.tensor(dims)
+        q[:, hs, d] = QMAG * signs.float()[:, None]
+        k[:, hs, d] = levels.float().t()
+        for (h, a, b) in twins:
+            k[b, h] = k[a, h]
+    finally:
+        torch.set_num_threads(threads)
     q, k, v = rnd(q.to(device), fmt), rnd(k.to(device), fmt), rnd(v.to(device), fmt)      # (rounded where the tests compute: nothing large on the host's cores)
     return Case(name, q, k, v, fmt, causal_offset, dims)
 
@@ -183,6 +195,128 @@ def dense_cases(Sq, Sk, H, causal_offset, fmt, device="cpu"):
     for i in range(0, len(tw), H):
         grp = [tw[min(i + h, len(tw) - 1)] for h in range(H)]
         yield build("twin" + str(tuple(grp)), torch.stack([twin(Sk, a, b) for a, b in grp]), plus, twins=[(h, a, b) for h, (a, b) in enumerate(grp)], seed=40 + i, **kw)
+
+
+# ---- batched launches: the samples of ONE launch (grid.z), every sample a pattern of its own ------------------------------------------------------
+ADV = SPIKE + 50.0            # level of the adversarial key behind a short last sample: GAP-dominant over every level of a spike case
+
+
+class Batch:
+    """The samples of one batched launch.  q (B, Sq, H, 64), k, v (B, Sk, H, 64) float32 holding values of `fmt`: what the full-length buffers of the launch
+    hold; cases[b]: the Case sample b must compute (reference(), analyse() and bound() run on it).  last_len > 0: the last sample is cases[-1] of shape
+    (last_len, last_len) in the leading rows of q[-1], k[-1], v[-1]; behind them sit the rows of a filler pattern, and key `last_len` is adversarial: level ADV
+    in every head's dimension and V far from every other key's, so a row that wrongly saw it returns that V.  Nothing in here is modified after stack()."""
+    def __init__(self, name, cases, q, k, v, causal_offset, last_len, fmt):
+        self.name, self.cases, self.q, self.k, self.v, self.causal_offset, self.last_len, self.fmt = name, cases, q, k, v, causal_offset, last_len, fmt
+        self.B, self.Sq, self.H = q.shape[0], q.shape[1], q.shape[2]
+        self.Sk = k.shape[1]
+
+    def rows(self, b):
+        """(query rows, keys) of sample b"""
+        return (self.cases[b].q.shape[0], self.cases[b].k.shape[0])
+
+
+def stack(name, cases, last=None, shared_q=None, Sq=None, Sk=None):
+    """Stacks Cases of one shape (Sq, Sk) into a Batch.  last: a shorter Case of shape (L, L) that becomes the last sample (see Batch); Sq, Sk are needed when
+    `cases` is empty.  shared_q (Sq, H, 64): every sample takes this query instead of its own (one Q for all samples, sample stride 0): the Cases are rebuilt on it."""
+    cases = list(cases)
+    if shared_q is not None:
+        cases = [Case(c.name, shared_q, c.k, c.v, c.fmt, c.causal_offset, c.dims) for c in cases]
+    first = cases[0] if cases else last
+    Sq, Sk = (cases[0].q.shape[0], cases[0].k.shape[0]) if cases else (Sq, Sk)
+    assert all(c.q.shape[0] == Sq and c.k.shape[0] == Sk and c.fmt == first.fmt and c.causal_offset == first.causal_offset for c in cases)
+    qs, ks, vs = [c.q for c in cases], [c.k for c in cases], [c.v for c in cases]
+    last_len = -1
+    if last is not None:
+        L, H, dev = last.q.shape[0], last.q.shape[1], last.q.device
+        assert last.k.shape[0] == L and L <= min(Sq, Sk) and last.fmt == first.fmt and last.causal_offset == first.causal_offset
+        last_len = L
+        fill = build("filler", stairs_down(Sk)[None].expand(H, Sk).clone(), torch.ones(Sq), last.fmt, causal_offset=last.causal_offset, dims=last.dims, seed=99, device=dev)
+        q, k, v = fill.q.clone(), fill.k.clone(), fill.v.clone()
+        q[:L], k[:L], v[:L] = last.q, last.k, last.v
+        if L < Sk:
+            k[L, torch.arange(H, device=dev), torch.tensor(last.dims, device=dev)] = ADV
+            v[L] = rnd(v[L] + 4.0, last.fmt)
+        qs.append(q); ks.append(k); vs.append(v)
+        cases = cases + [last]
+    return Batch(name, cases, torch.stack(qs), torch.stack(ks), torch.stack(vs), first.causal_offset, last_len, first.fmt)
+
+
+def spike_case(Sq, Sk, positions, fmt, causal_offset, seed, device="cpu"):
+    """One spike per head at positions[h] (signs all +)."""
+    return build("spike" + str(tuple(positions)), torch.stack([spike(Sk, j) for j in positions]), torch.ones(Sq), fmt, causal_offset=causal_offset, seed=seed, device=device)
+
+
+def short_case(L, H, fmt, causal_offset, device="cpu"):
+    """The shortened last sample of a batch, shape (L, L): spikes from spike_positions_dense(L, L, .) -- head 0's at L - 1, the last key the sample has, the other
+    heads' walk down the list from there."""
+    pos = spike_positions_dense(L, L, causal_offset)
+    assert pos[-1] == L - 1
+    grp = [pos[max(len(pos) - 1 - h, 0)] for h in range(H)]
+    return spike_case(L, L, grp, fmt, causal_offset, seed=70 + L, device=device)
+
+
+# the launches of tests/test_gpu_attention_batched.py; tests/test_attn_cases_host.py checks every one of them on the host
+LAYOUT_LAUNCHES = [      # (layout, Sq, Sk, causal_offset)
+    ("interleaved", 130, 130, -1), ("interleaved", 257, 257, -1), ("interleaved", 96, 65, -1),
+    ("blocks", 128, 128, -1), ("blocks", 257, 257, 0), ("blocks", 130, 130, 0),
+    ("cross", 70, 300, -1), ("cross", 96, 65, -1),
+    ("planes", 257, 257, 0), ("planes", 130, 130, 0), ("planes", 128, 128, 0)]
+LAST_LEN_LAUNCHES = [(257, L) for L in (193, 249, 256, 257)] + [(130, L) for L in (1, 63, 64, 65, 96, 97, 129)]      # (T, last_len), each causal and not
+TAIL_LAUNCHES = [(T, nt) for T in (130, 257) for nt in (1, 2, 34, 64)]                                              # (T, rows of the tail chain)
+BATCH_H = 2
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_case_list(Sq, Sk, causal_offset, fmt, device):
+    """dense_cases at H = BATCH_H, built once per shape and shared by every launch that stacks them (nobody modifies a Case)."""
+    return tuple(dense_cases(Sq, Sk, BATCH_H, causal_offset, fmt, device=device))
+
+
+def layout_batch(layout, Sq, Sk, causal_offset, fmt, device="cpu"):
+    """Every pattern of dense_cases as a sample of its own; `cross`: one Q for all samples (the zigzag's alternating signs: every pattern then has rows that
+    look at its levels from both sides)."""
+    cases = list(_dense_case_list(Sq, Sk, causal_offset, fmt, device))
+    shared = next(c for c in cases if c.name == "zigzag").q if layout == "cross" else None
+    return stack(f"{layout} {(Sq, Sk, causal_offset)} {fmt}", cases, shared_q=shared)
+
+
+def _pick2(cases, i):
+    """Two full-length samples for a batch of 3: the zigzag (the one pattern whose query rows differ: a launch without it cannot see a query row shifted) and
+    another one of the remaining patterns for every i."""
+    rest = [c for c in cases if c.name != "zigzag"]
+    return [next(c for c in cases if c.name == "zigzag"), rest[i % len(rest)]]
+
+
+def last_len_batch(T, L, causal_offset, fmt, device="cpu"):
+    """B = 3: two full (T, T) samples and the short_case of L rows."""
+    cases = list(_dense_case_list(T, T, causal_offset, fmt, device))
+    return stack(f"last_len {(T, L, causal_offset)} {fmt}", _pick2(cases, L), last=short_case(L, BATCH_H, fmt, causal_offset, device=device))
+
+
+def tail_batch(T, nt, fmt, device="cpu"):
+    """B = 3 full causal (T, T) samples; the last one has its spikes on both sides of the cut between the main chain's rows and the tail chain's:
+    key T - nt - 1 (head 0: the last key the main chain has) and key T - nt (head 1: the first one it must not read)."""
+    cases = list(_dense_case_list(T, T, 0, fmt, device))
+    cut = spike_case(T, T, [max(T - nt - 1, 0), T - nt], fmt, 0, seed=90 + nt, device=device)
+    return stack(f"tail {(T, nt)} {fmt}", _pick2(cases, nt) + [cut])
+
+
+def wrong_variants(batch, b):
+    """The Cases a kernel with one of four mistakes would compute for sample b, as (name, Case) -- judged against cases[b] each must exceed the bound somewhere
+    in the launch (test_attn_cases_host.py).  From the launch's full-length buffers:
+      q_shift      query rows shifted by one (row i computes row i + 1)
+      k_shift+-    K rows shifted by one against V (a K row stride / offset off by one row)
+      sk_full      (the short last sample) every key of the full-length buffers instead of last_len; under a causal mask the rows that are kept never see
+                   those keys whatever Sk is, so there the mistake is the mask letting ONE more key in (row last_len - 1 sees key last_len)."""
+    c = batch.cases[b]
+    nq, nk = batch.rows(b)
+    q, k, v = batch.q[b], batch.k[b], batch.v[b]
+    mk = lambda name, q_, k_, v_, off=c.causal_offset: (name, Case(name, q_, k_, v_, c.fmt, off, c.dims))
+    out = [mk("q_shift", torch.roll(q, -1, 0)[:nq], k[:nk], v[:nk]), mk("k_shift+", q[:nq], torch.roll(k, -1, 0)[:nk], v[:nk]), mk("k_shift-", q[:nq], torch.roll(k, 1, 0)[:nk], v[:nk])]
+    if batch.last_len > 0 and b == batch.B - 1 and nk < batch.Sk:
+        out.append(mk("sk_full", q[:nq], k, v) if c.causal_offset < 0 else mk("sk_full", q[:nq], k, v, c.causal_offset + 1))
+    return out
 
 
 def decode_slots(length, chunks=16):
