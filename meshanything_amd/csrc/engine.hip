@@ -44,6 +44,7 @@
 #include "pc_normals.hpp"
 #include "pc_fps.hpp"
 #include "pc_grid.hpp"
+#include "pc_radius.hpp"
 #include "pc_cluster.hpp"
 #include "pc_smooth.hpp"
 #include "pc_upsample.hpp"
@@ -1135,24 +1136,30 @@ int ma_op_pc_fps(const float* ref, int N, int ref_ld, int n, int start, int form
 // ---- neighbours of every point over a cell grid, for statistical outlier removal (csrc/pc_grid.hpp) -------------------------------------
 static_assert(MA_PC_GRID_MAX_POINTS == pcg::MAX_POINTS && MA_PC_GRID_MAX_DIM == pcg::MAX_DIM && MA_PC_GRID_MAX_CELLS == pcg::MAX_CELLS,
               "the header's limits are the kernels'");
-static bool pc_grid_shape_ok(int N, int k, int nx, int ny, int nz) {
-    return k >= MA_PC_KNN_MIN_K && k <= MA_PC_KNN_MAX_K && N >= k && N <= MA_PC_GRID_MAX_POINTS && nx >= 1 && nx <= MA_PC_GRID_MAX_DIM && ny >= 1 &&
-           ny <= MA_PC_GRID_MAX_DIM && nz >= 1 && nz <= MA_PC_GRID_MAX_DIM && (int64_t)nx * ny * nz <= MA_PC_GRID_MAX_CELLS;
+static bool grid_dims_ok(int nx, int ny, int nz) {
+    return nx >= 1 && nx <= MA_PC_GRID_MAX_DIM && ny >= 1 && ny <= MA_PC_GRID_MAX_DIM && nz >= 1 && nz <= MA_PC_GRID_MAX_DIM &&
+           (int64_t)nx * ny * nz <= MA_PC_GRID_MAX_CELLS;
 }
 
-size_t ma_pc_knn_grid_workspace_bytes(int N, int k, int nx, int ny, int nz) { return pc_grid_shape_ok(N, k, nx, ny, nz) ? pcg::layout(N, nx * ny * nz).bytes : 0; }
+static bool pc_grid_n_ok(int N, int k) { return k >= MA_PC_KNN_MIN_K && k <= MA_PC_KNN_MAX_K && N >= k && N <= MA_PC_GRID_MAX_POINTS; }
+
+// the grid of a grid op, checked; n_ok / need: the op's own test of N (and k) and its wording
+static pcg::Grid checked_grid(const std::string& op, bool n_ok, const char* need, const float* origin, float cell, const int32_t* dims) {
+    if (!n_ok || !grid_dims_ok(dims[0], dims[1], dims[2])) throw MaError(MA_ERR_INVALID, op + ": need " + need + ", every dim in 1..128 and at most 2^21 cells");
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, op + ": origin must be finite");
+    if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, op + ": cell must be finite and > 0");
+    return pcg::Grid{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
+}
+
+size_t ma_pc_knn_grid_workspace_bytes(int N, int k, int nx, int ny, int nz) { return pc_grid_n_ok(N, k) && grid_dims_ok(nx, ny, nz) ? pcg::layout(N, nx * ny * nz).bytes : 0; }
 
 int ma_op_pc_knn_grid(const float* ref, int N, int ref_ld, int k, const float* origin, float cell, const int32_t* dims, int32_t* nbr_idx, float* nbr_d2,
                       double* mean_dist, void* workspace, size_t ws_bytes, void* stream) {
     return guarded(nullptr, [&] {
         if (!ref || !origin || !dims || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: null pointer");
         if (!nbr_idx && !nbr_d2 && !mean_dist) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: no output: give at least one of nbr_idx, nbr_d2 and mean_dist");
-        if (!pc_grid_shape_ok(N, k, dims[0], dims[1], dims[2]))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: need 3 <= k <= 32, k <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        const pcg::Grid g = checked_grid("ma_op_pc_knn_grid", pc_grid_n_ok(N, k), "3 <= k <= 32, k <= N <= 2^22", origin, cell, dims);
         if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: ref_ld must be 3 or 6");
-        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: origin must be finite");
-        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: cell must be finite and > 0");
-        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
         if (ws_bytes < pcg::layout(N, pcg::cells_of(g)).bytes)
             throw MaError(MA_ERR_INVALID, "ma_op_pc_knn_grid: workspace smaller than ma_pc_knn_grid_workspace_bytes(N, k, nx, ny, nz)");
         HIP_CHECK(pcg::launch_build(ref, N, ref_ld, g, workspace, reinterpret_cast<hipStream_t>(stream)));
@@ -1160,50 +1167,62 @@ int ma_op_pc_knn_grid(const float* ref, int N, int ref_ld, int k, const float* o
     });
 }
 
+// ---- the radius searches over the cell grid: what cluster, smooth and upsample share on the host (csrc/pc_radius.hpp) ------------------------
+static bool pc_radius_shape_ok(int N, int nx, int ny, int nz) { return N >= 1 && N <= MA_PC_GRID_MAX_POINTS && grid_dims_ok(nx, ny, nz); }
 
-// ---- Euclidean clustering over the cell grid (csrc/pc_cluster.hpp) ------------------------------------------------------------------------
-static bool pc_cluster_shape_ok(int N, int nx, int ny, int nz) {
-    return N >= 1 && N <= MA_PC_GRID_MAX_POINTS && nx >= 1 && nx <= MA_PC_GRID_MAX_DIM && ny >= 1 && ny <= MA_PC_GRID_MAX_DIM && nz >= 1 &&
-           nz <= MA_PC_GRID_MAX_DIM && (int64_t)nx * ny * nz <= MA_PC_GRID_MAX_CELLS;
+// called before the op's own checks, so that an N outside the limits is reported as that and not by a check that multiplies by it
+static pcg::Grid radius_grid(const std::string& op, int N, const float* origin, float cell, const int32_t* dims) {
+    return checked_grid(op, N >= 1 && N <= MA_PC_GRID_MAX_POINTS, "1 <= N <= 2^22", origin, cell, dims);
 }
 
-size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcc::layout(N, nx * ny * nz).bytes : 0; }
+// From the checked grid and the op's own checked arguments to the point where the op's long kernel may be launched: the ratio rule (`what`
+// names the radius in it), r2 = fl32(radius * radius) with radius as float32, the rings and the host's test that they suffice, the workspace
+// size (need_bytes: the op's layout), the build and the pair bound, its read-back into *pair_bound, and the cap.  Returns r2.  zeroed, if
+// given: a result of the op that is 0 from the moment the checks have passed (upsample's total).
+static float radius_prologue(const std::string& name, const char* what, const float* ref, int N, int ref_ld, const pcg::Grid& g, double radius,
+                             uint64_t max_pairs, void* workspace, size_t workspace_bytes, size_t need_bytes, uint64_t* pair_bound, uint64_t* zeroed,
+                             hipStream_t s) {
+    const std::string op = "ma_op_pc_" + name;
+    if (!(radius / (double)g.cell <= (double)pcr::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, op + ": " + what + " / cell must be at most 8");
+    volatile float rf = (float)radius;
+    volatile float r2 = rf * rf;
+    const int R = pcr::rings(rf, g.cell);
+    if (!pcr::rings_suffice(g, r2, R))
+        throw MaError(MA_ERR_INVALID, op + ": the float32 faces of this grid do not separate cells " + std::to_string(R) +
+                                          " apart by more than the radius (origin too large against cell): the pair bound would not hold");
+    if (workspace_bytes < need_bytes) throw MaError(MA_ERR_INVALID, op + ": workspace smaller than ma_pc_" + name + "_workspace_bytes(N, nx, ny, nz)");
+    const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
+    if (zeroed) *zeroed = 0;
+    HIP_CHECK(pcr::launch_bound(ref, N, ref_ld, g, R, workspace, s));
+    unsigned long long total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, pcr::total_of(N, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (pair_bound) *pair_bound = total;
+    if (total > cap)
+        throw MaError(MA_ERR_INVALID, op + ": the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
+                                          ": use a smaller radius or fewer points");
+    return r2;
+}
+
+// ---- Euclidean clustering over the cell grid (csrc/pc_cluster.hpp) ------------------------------------------------------------------------
+size_t ma_pc_cluster_workspace_bytes(int N, int nx, int ny, int nz) { return pc_radius_shape_ok(N, nx, ny, nz) ? pcc::layout(N, nx * ny * nz).bytes : 0; }
 
 int ma_op_pc_cluster(const float* ref, int N, int ref_ld, float radius, const float* origin, float cell, const int32_t* dims, uint64_t max_pairs,
                      int32_t* labels, int32_t* sizes, uint64_t* pairs_bound, void* workspace, size_t workspace_bytes, void* stream) {
     return guarded(nullptr, [&] {
         if (!ref || !origin || !dims || !labels || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: null pointer");
-        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        const pcg::Grid g = radius_grid("ma_op_pc_cluster", N, origin, cell, dims);
         if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: ref_ld must be 3 or 6");
         if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: radius must be finite and > 0");
-        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: origin must be finite");
-        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: cell must be finite and > 0");
-        if (!((double)radius / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: radius / cell must be at most 8");
-        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
-        volatile float r2 = radius * radius;
-        const int R = pcc::rings(radius, cell);
-        if (!pcc::rings_suffice(g, r2, R))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the float32 faces of this grid do not separate cells " + std::to_string(R) +
-                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
-        if (workspace_bytes < pcc::layout(N, pcg::cells_of(g)).bytes)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: workspace smaller than ma_pc_cluster_workspace_bytes(N, nx, ny, nz)");
-        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        HIP_CHECK(pcc::launch_bound(ref, N, ref_ld, g, R, workspace, s));
-        unsigned long long total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, pcc::total_of(N, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (pairs_bound) *pairs_bound = total;
-        if (total > cap)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_cluster: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
-                                              ": use a smaller radius or fewer points");
+        const float r2 = radius_prologue("cluster", "radius", ref, N, ref_ld, g, (double)radius, max_pairs, workspace, workspace_bytes,
+                                         pcc::layout(N, pcg::cells_of(g)).bytes, pairs_bound, nullptr, s);
         HIP_CHECK(pcc::launch_hook_flatten(N, r2, g, labels, sizes, workspace, s));
     });
 }
 
 // ---- moving-least-squares smoothing over the cell grid (csrc/pc_smooth.hpp) -----------------------------------------------------------------
-size_t ma_pc_smooth_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcs::layout(N, nx * ny * nz).bytes : 0; }
+size_t ma_pc_smooth_workspace_bytes(int N, int nx, int ny, int nz) { return pc_radius_shape_ok(N, nx, ny, nz) ? pcr::layout(N, nx * ny * nz).bytes : 0; }
 
 int ma_op_pc_smooth(const float* ref, int N, int ref_ld, float radius, const float* origin, float cell, const int32_t* dims, int min_count,
                     uint64_t max_pairs, double* moved, double* normals, double* eigvals, int32_t* count, uint64_t* pair_bound, void* workspace,
@@ -1212,39 +1231,20 @@ int ma_op_pc_smooth(const float* ref, int N, int ref_ld, float radius, const flo
         if (!ref || !origin || !dims || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: null pointer");
         if (!moved && !normals && !eigvals && !count)
             throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: no output: give at least one of moved, normals, eigvals and count");
-        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        const pcg::Grid g = radius_grid("ma_op_pc_smooth", N, origin, cell, dims);
         if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: ref_ld must be 3 or 6");
         if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: radius must be finite and > 0");
         if (min_count < pcs::MIN_COUNT) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: min_count must be at least 3, the points a plane takes");
-        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: origin must be finite");
-        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: cell must be finite and > 0");
-        if (!((double)radius / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: radius / cell must be at most 8");
-        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
-        volatile float r2 = radius * radius;
-        const int R = pcc::rings(radius, cell);
-        if (!pcc::rings_suffice(g, r2, R))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: the float32 faces of this grid do not separate cells " + std::to_string(R) +
-                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
-        if (workspace_bytes < pcs::layout(N, pcg::cells_of(g)).bytes)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: workspace smaller than ma_pc_smooth_workspace_bytes(N, nx, ny, nz)");
-        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        HIP_CHECK(pcs::launch_bound(ref, N, ref_ld, g, R, workspace, s));
-        unsigned long long total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, pcs::total_of(N, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (pair_bound) *pair_bound = total;
-        if (total > cap)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_smooth: the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
-                                              ": use a smaller radius or fewer points");
+        const float r2 = radius_prologue("smooth", "radius", ref, N, ref_ld, g, (double)radius, max_pairs, workspace, workspace_bytes,
+                                         pcr::layout(N, pcg::cells_of(g)).bytes, pair_bound, nullptr, s);
         HIP_CHECK(pcs::launch_smooth(N, r2, g, min_count, moved, normals, eigvals, count, workspace, s));
     });
 }
 
 // ---- upsampling: lattice points in every row's plane, kept where the row is the nearest (csrc/pc_upsample.hpp) ------------------------------
 static_assert(MA_PC_UPSAMPLE_MAX_M == pcu::MAX_M, "the header's limit is the kernels'");
-size_t ma_pc_upsample_workspace_bytes(int N, int nx, int ny, int nz) { return pc_cluster_shape_ok(N, nx, ny, nz) ? pcu::layout(N, nx * ny * nz).bytes : 0; }
+size_t ma_pc_upsample_workspace_bytes(int N, int nx, int ny, int nz) { return pc_radius_shape_ok(N, nx, ny, nz) ? pcu::layout(N, nx * ny * nz).bytes : 0; }
 
 int ma_op_pc_upsample(const float* ref, int N, int ref_ld, const double* normals, const uint8_t* active, int m, double step, const float* origin, float cell,
                       const int32_t* dims, uint64_t max_pairs, int32_t* counts, float* out_xyz, int32_t* out_seed, uint64_t capacity, uint64_t* total,
@@ -1252,8 +1252,7 @@ int ma_op_pc_upsample(const float* ref, int N, int ref_ld, const double* normals
     return guarded(nullptr, [&] {
         if (!ref || !normals || !origin || !dims || !total || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: null pointer");
         if (!out_xyz && out_seed) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: out_seed without out_xyz: a count-only call takes neither");
-        if (!pc_cluster_shape_ok(N, dims[0], dims[1], dims[2]))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: need 1 <= N <= 2^22, every dim in 1..128 and at most 2^21 cells");
+        const pcg::Grid g = radius_grid("ma_op_pc_upsample", N, origin, cell, dims);
         if (ref_ld < 3) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: ref_ld must be at least 3");
         if (m < 1 || m > pcu::MAX_M) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: m must be in 1..64");
         if ((int64_t)N * (2 * m + 1) * (2 * m + 1) > pcu::MAX_SLOTS)
@@ -1261,28 +1260,9 @@ int ma_op_pc_upsample(const float* ref, int N, int ref_ld, const double* normals
         volatile float radius = (float)((double)m * step);
         if (!std::isfinite(step) || !(step > 0.0) || !std::isfinite(radius) || !(radius > 0.f))
             throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: step must be finite and > 0, and m * step a positive finite float32");
-        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: origin must be finite");
-        if (!std::isfinite(cell) || !(cell > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: cell must be finite and > 0");
-        if (!((double)m * step / (double)cell <= (double)pcc::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: m * step / cell must be at most 8");
-        const pcg::Grid g{origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2]};
-        volatile float r2 = radius * radius;
-        const int R = pcc::rings(radius, cell);
-        if (!pcc::rings_suffice(g, r2, R))
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the float32 faces of this grid do not separate cells " + std::to_string(R) +
-                                              " apart by more than the radius (origin too large against cell): the pair bound would not hold");
-        if (workspace_bytes < pcu::layout(N, pcg::cells_of(g)).bytes)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: workspace smaller than ma_pc_upsample_workspace_bytes(N, nx, ny, nz)");
-        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        *total = 0;
-        HIP_CHECK(pcu::launch_bound(ref, N, ref_ld, g, R, workspace, s));
-        unsigned long long bound = 0;
-        HIP_CHECK(hipMemcpyAsync(&bound, pcu::total_of(N, g, workspace), sizeof(bound), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (pair_bound) *pair_bound = bound;
-        if (bound > cap)
-            throw MaError(MA_ERR_INVALID, "ma_op_pc_upsample: the pair bound " + std::to_string(bound) + " exceeds max_pairs " + std::to_string(cap) +
-                                              ": use a smaller radius or fewer points");
+        radius_prologue("upsample", "m * step", ref, N, ref_ld, g, (double)m * step, max_pairs, workspace, workspace_bytes,
+                        pcu::layout(N, pcg::cells_of(g)).bytes, pair_bound, total, s);
         HIP_CHECK(pcu::launch_count(ref, N, ref_ld, normals, active, m, step, g, out_xyz ? nullptr : counts, workspace, s));
         long long kept = 0;
         HIP_CHECK(hipMemcpyAsync(&kept, pcu::offs_of(N, g, workspace) + N, sizeof(kept), hipMemcpyDeviceToHost, s));

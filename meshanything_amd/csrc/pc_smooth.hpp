@@ -14,9 +14,9 @@
 //   a row STAYS, moved = (double)q, normal (0, 0, 1), eigenvalues 0, when count < min_count, when all its neighbours coincide, or when
 //     anything comes out non-finite.
 //
-// Build: pcg::launch_build, unchanged.  Pair bound: pcc::bound_kernel and the host's pcc::rings_suffice, unchanged; the argument in the
-// header of pc_cluster.hpp carries over word for word, the neighbour rule being its link rule.  The bound is read back by the host and
-// compared with max_pairs before the smooth kernel is launched.
+// Build: pcg::launch_build, unchanged.  Pair bound: pcr::launch_bound and the host's pcr::rings_suffice (pc_radius.hpp, whose argument
+// is about a walk with limit r2, which this one is).  The workspace is pcr::layout, nothing of this op's own.  The bound is read back by
+// the host and compared with max_pairs before the smooth kernel is launched.
 //
 // Smooth (smooth_kernel): one query per thread, 256 per workgroup, queries in cell order (thread t owns record t) so that a wave's lanes
 // walk the same cells; the ring and segment walk and the radius stop rule of pcc::hook_kernel.  The ten float64 accumulators and the
@@ -31,28 +31,15 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "pc_cluster.hpp"
 #include "pc_grid.hpp"
 #include "pc_normals.hpp"
+#include "pc_radius.hpp"
 
 namespace ma {
 namespace pcs {
 
 constexpr int THREADS = pcg::THREADS;
 constexpr int MIN_COUNT = 3;
-
-struct Layout {
-    size_t total, bytes;
-};
-
-// pcg::layout(N, cells) | the 64-bit total of the pair bound
-inline Layout layout(int N, int cells) {
-    Layout l;
-    size_t o = pcg::layout(N, cells).bytes;
-    l.total = o; o += wt::align256(sizeof(unsigned long long));
-    l.bytes = o;
-    return l;
-}
 
 __global__ __launch_bounds__(THREADS) void smooth_kernel(const float4* __restrict__ sorted, const int* __restrict__ start, const int* __restrict__ cell_id,
                                                          int N, float r2, pcg::Grid g, int min_count, double* __restrict__ moved,
@@ -134,24 +121,6 @@ __global__ __launch_bounds__(THREADS) void smooth_kernel(const float4* __restric
     if (normals) { double* o = normals + 3 * (int64_t)qi; o[0] = nx; o[1] = ny; o[2] = nz; }
     if (eigvals) { double* o = eigvals + 3 * (int64_t)qi; o[0] = l0; o[1] = l1; o[2] = l2; }
     if (count) count[qi] = cnt;
-}
-
-inline unsigned long long* total_of(int N, const pcg::Grid& g, void* workspace) {
-    return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + layout(N, pcg::cells_of(g)).total);
-}
-
-// build, and the pair bound of pc_cluster.hpp into the workspace's total
-inline hipError_t launch_bound(const float* ref, int N, int ref_ld, const pcg::Grid& g, int R, void* workspace, hipStream_t s) {
-    const int cells = pcg::cells_of(g);
-    char* ws = static_cast<char*>(workspace);
-    unsigned long long* total = total_of(N, g, workspace);
-    hipError_t e = pcg::launch_build(ref, N, ref_ld, g, workspace, s);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(total, 0, sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pcc::bound_kernel, dim3((unsigned)((cells + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
-                       reinterpret_cast<const int*>(ws + pcg::layout(N, cells).start), N, g, R, total);
-    return hipGetLastError();
 }
 
 inline hipError_t launch_smooth(int N, float r2, const pcg::Grid& g, int min_count, double* moved, double* normals, double* eigvals, int* count,

@@ -38,9 +38,9 @@
 // the total -> the host reads the total back -> emit pass (lattice_kernel<true>) recomputes the keep tests, the same code on the same
 // inputs, and writes at offset[seed] + position.  Every write is also guarded by the capacity.  No atomics beyond pcg::launch_build's.
 //
-// Pair bound: pcc::bound_kernel and pcc::rings_suffice with radius fl32(m * step), read back and compared with max_pairs before the long
-// kernels, as in pc_smooth.hpp.  Here it is the guard against a radius the size of the cloud and not a count of this op's keys: a
-// candidate is no row, and its walk ends at the first row that precedes its seed, typically inside its own cell.
+// Pair bound: pcr::launch_bound and pcr::rings_suffice (pc_radius.hpp) with radius fl32(m * step), read back and compared with max_pairs
+// before the long kernels, as in pc_smooth.hpp.  Here it is the guard against a radius the size of the cloud and not a count of this
+// op's keys: a candidate is no row, and its walk ends at the first row that precedes its seed, typically inside its own cell.
 //
 // Non-finite input through the raw ABI: such a seed is skipped; as a record a non-finite row has key NaN -> +inf or +inf and precedes a
 // seed only at an infinite ds.  Every read stays inside the records and the cell starts (pc_grid.hpp), and row indices read from the
@@ -50,8 +50,8 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "pc_cluster.hpp"
 #include "pc_grid.hpp"
+#include "pc_radius.hpp"
 #include "watertight.hpp"
 
 namespace ma {
@@ -63,14 +63,13 @@ constexpr int MAX_M = 64;
 constexpr int64_t MAX_SLOTS = int64_t(1) << 31;      // N * (2m+1)^2
 
 struct Layout {
-    size_t total, offs, scan, bytes;
+    size_t offs, scan, bytes;
 };
 
-// pcg::layout(N, cells) | the 64-bit total of the pair bound | offs (N + 1) int64: the counts, then their exclusive scan | the scan's tiles
+// pcr::layout(N, cells) | offs (N + 1) int64: the counts, then their exclusive scan | the scan's tiles
 inline Layout layout(int N, int cells) {
     Layout l;
-    size_t o = pcg::layout(N, cells).bytes;
-    l.total = o; o += wt::align256(sizeof(unsigned long long));
+    size_t o = pcr::layout(N, cells).bytes;
     l.offs = o;  o += wt::align256(((size_t)N + 1) * sizeof(int64_t));
     l.scan = o;  o += wt::align256((size_t)wt::scan_ws_elems((int64_t)N + 1) * sizeof(int64_t));
     l.bytes = o;
@@ -202,26 +201,8 @@ __global__ __launch_bounds__(THREADS) void lattice_kernel(const float* __restric
     }
 }
 
-inline unsigned long long* total_of(int N, const pcg::Grid& g, void* workspace) {
-    return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + layout(N, pcg::cells_of(g)).total);
-}
-
 inline int64_t* offs_of(int N, const pcg::Grid& g, void* workspace) {
     return reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + layout(N, pcg::cells_of(g)).offs);
-}
-
-// build, and the pair bound of pc_cluster.hpp into the workspace's total
-inline hipError_t launch_bound(const float* ref, int N, int ref_ld, const pcg::Grid& g, int R, void* workspace, hipStream_t s) {
-    const int cells = pcg::cells_of(g);
-    char* ws = static_cast<char*>(workspace);
-    unsigned long long* total = total_of(N, g, workspace);
-    hipError_t e = pcg::launch_build(ref, N, ref_ld, g, workspace, s);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(total, 0, sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pcc::bound_kernel, dim3((unsigned)((cells + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
-                       reinterpret_cast<const int*>(ws + pcg::layout(N, cells).start), N, g, R, total);
-    return hipGetLastError();
 }
 
 // the count pass and the scan; afterwards offs[N] (device) is the total.  counts: written here only by a count-only call

@@ -72,6 +72,60 @@ def _check_cloud(points):
         raise ValueError(f"need 1 <= N <= 2^22 points, got N = {points.shape[0]}")
 
 
+# ---- what every radius search over the grid shares (euclidean_clusters, pc_smooth.smooth_points, pc_upsample.upsample_points) ----------
+def check_max_pairs(max_pairs) -> int:
+    """The check on max_pairs; returns the cap the library takes, 0 = its own."""
+    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
+        raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
+    return 0 if max_pairs is None else int(max_pairs)
+
+
+def check_radius_grid(grid, radius):
+    """An explicit grid, checked as `pc_outliers._check_grid` does and against the ratio rule; None stays None."""
+    if grid is None:
+        return None
+    grid = _check_grid(grid)
+    if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
+        raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
+    return grid
+
+
+def grid_workspace(lib, op: str, ref: torch.Tensor, radius: float, grid):
+    """For ma_op_pc_<op> on the contiguous device cloud `ref`: the grid (None = `choose_cluster_grid` of a host copy, which must be
+    finite) as the three ctypes arguments (origin, cell, dims), and the workspace -> (grid arguments, workspace tensor, its bytes)."""
+    N = ref.shape[0]
+    if grid is None:
+        host = ref[:, :3].cpu().numpy()
+        if not np.isfinite(host).all():
+            raise ValueError("the point cloud has non-finite coordinates")
+        grid = choose_cluster_grid(host, radius)
+    origin, cell, dims = grid
+    nbytes = getattr(lib, f"ma_pc_{op}_workspace_bytes")(N, int(dims[0]), int(dims[1]), int(dims[2]))
+    if nbytes == 0:
+        raise ValueError(f"outside the limits of ma_op_pc_{op}: N = {N}, dims = {dims.tolist()}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
+    return ((C.c_float * 3)(*origin.tolist()), float(cell), (C.c_int32 * 3)(*dims.tolist())), ws, nbytes
+
+
+def check_pair_bound(fn: str, rc: int, bound: int, cap: int, N: int, radius: float):
+    """The library refused the call because its pair bound exceeds the cap: a ValueError that names both."""
+    if rc != _lib.MA_OK and bound > (cap or MAX_PAIRS):
+        raise ValueError(f"{fn}: the pair bound {bound} exceeds max_pairs {cap or MAX_PAIRS} (N = {N}, radius {radius}): "
+                         "use a smaller radius or fewer points")
+
+
+def check_host_cloud(xyz, noun: str) -> np.ndarray:
+    """The checks of split_rows, smooth_rows and upsample_rows on the cloud that need no device; returns xyz as an array."""
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
+        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
+    if not 1 <= xyz.shape[0] <= MAX_POINTS:
+        raise ValueError(f"{noun} needs 1 <= N <= 2^22 points, got N = {xyz.shape[0]}")
+    if not np.isfinite(xyz[:, :3]).all():
+        raise ValueError("the point cloud has non-finite coordinates")
+    return xyz
+
+
 def euclidean_clusters(points: torch.Tensor, radius, grid=None, want=("labels",), max_pairs=None):
     """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns, finite -> a dict with the entries named in `want`: "labels"
     (N) int32, labels[i] = the smallest row index in the connected component of i, rows i and j being linked iff
@@ -84,38 +138,21 @@ def euclidean_clusters(points: torch.Tensor, radius, grid=None, want=("labels",)
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in WANT for w in want):
         raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
-    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
-        raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
-    if grid is not None:
-        grid = _check_grid(grid)
-        if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
-            raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
+    cap = check_max_pairs(max_pairs)
+    grid = check_radius_grid(grid, radius)
     _need_cuda(points, "euclidean_clusters")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
         ref = points.contiguous()
         N = ref.shape[0]
-        if grid is None:
-            host = ref[:, :3].cpu().numpy()
-            if not np.isfinite(host).all():
-                raise ValueError("the point cloud has non-finite coordinates")
-            grid = choose_cluster_grid(host, radius)
-        origin, cell, dims = grid
-        nbytes = lib.ma_pc_cluster_workspace_bytes(N, int(dims[0]), int(dims[1]), int(dims[2]))
-        if nbytes == 0:
-            raise ValueError(f"outside the limits of ma_op_pc_cluster: N = {N}, dims = {dims.tolist()}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        grid_args, ws, nbytes = grid_workspace(lib, "cluster", ref, radius, grid)
         labels = torch.empty(N, dtype=torch.int32, device=dev)
         sizes = torch.empty(N, dtype=torch.int32, device=dev) if "sizes" in want else None
         bound = C.c_uint64(0)
-        cap = 0 if max_pairs is None else int(max_pairs)
-        rc = lib.ma_op_pc_cluster(ref.data_ptr(), N, ref.shape[1], radius, (C.c_float * 3)(*origin.tolist()), float(cell), (C.c_int32 * 3)(*dims.tolist()),
-                                  cap, labels.data_ptr(), None if sizes is None else sizes.data_ptr(), C.byref(bound), ws.data_ptr(), nbytes,
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != _lib.MA_OK and bound.value > (cap or MAX_PAIRS):
-            raise ValueError(f"euclidean_clusters: the pair bound {bound.value} exceeds max_pairs {cap or MAX_PAIRS} (N = {N}, radius {radius}): "
-                             "use a smaller radius or fewer points")
+        rc = lib.ma_op_pc_cluster(ref.data_ptr(), N, ref.shape[1], radius, *grid_args, cap, labels.data_ptr(), None if sizes is None else sizes.data_ptr(),
+                                  C.byref(bound), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        check_pair_bound("euclidean_clusters", rc, bound.value, cap, N, radius)
         _lib.check(rc)
     out = {"labels": labels, "sizes": sizes}
     return {w: out[w] for w in WANT if w in want}
@@ -141,25 +178,13 @@ def check_split_args(radius, min_points, mode) -> tuple:
     return radius, int(min_points), mode
 
 
-def check_cluster_cloud(xyz) -> np.ndarray:
-    """The checks of split_rows on the cloud that need no device; returns xyz as an array."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
-    if not 1 <= xyz.shape[0] <= MAX_POINTS:
-        raise ValueError(f"clustering needs 1 <= N <= 2^22 points, got N = {xyz.shape[0]}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
-    return xyz
-
-
 def split_rows(xyz, radius, min_points, mode, uid: str, device="cuda"):
     """xyz (N, >= 3) host array, only the first three columns are read (uploaded as float32) -> a list of row-index arrays (int64), one
     per kept component: the components of `euclidean_clusters` with at least min_points rows, in the order of `components`, each in the
     file's row order; mode "largest" keeps the first only.  Prints the clustering line of the command line.  No component of
     min_points rows is a ValueError that names the largest size."""
     radius, min_points, mode = check_split_args(radius, min_points, mode)
-    xyz = check_cluster_cloud(xyz)
+    xyz = check_host_cloud(xyz, "clustering")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("split_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")

@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_cluster import MAX_PAIRS, MAX_RADIUS_IN_CELLS, _check_cloud, check_radius, choose_cluster_grid
-from .pc_normals import MAX_POINTS, _need_cuda
-from .pc_outliers import _check_grid
+from .pc_cluster import (_check_cloud, check_host_cloud, check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid,
+                         grid_workspace)
+from .pc_normals import _need_cuda
 
 MIN_COUNT = 3                                                    # MA_PC_SMOOTH_MIN_COUNT: the points a plane takes
 DEFAULT_MIN_COUNT = 6
@@ -44,37 +44,21 @@ def smooth_points(points: torch.Tensor, radius, min_count=DEFAULT_MIN_COUNT, gri
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in WANT for w in want):
         raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
-    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
-        raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
-    if grid is not None:
-        grid = _check_grid(grid)
-        if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
-            raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
+    cap = check_max_pairs(max_pairs)
+    grid = check_radius_grid(grid, radius)
     _need_cuda(points, "smooth_points")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
         ref = points.contiguous()
         N = ref.shape[0]
-        if grid is None:
-            host = ref[:, :3].cpu().numpy()
-            if not np.isfinite(host).all():
-                raise ValueError("the point cloud has non-finite coordinates")
-            grid = choose_cluster_grid(host, radius)
-        origin, cell, dims = grid
-        nbytes = lib.ma_pc_smooth_workspace_bytes(N, int(dims[0]), int(dims[1]), int(dims[2]))
-        if nbytes == 0:
-            raise ValueError(f"outside the limits of ma_op_pc_smooth: N = {N}, dims = {dims.tolist()}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        grid_args, ws, nbytes = grid_workspace(lib, "smooth", ref, radius, grid)
         out = {w: torch.empty(N, dtype=torch.int32, device=dev) if w == "count" else torch.empty((N, 3), dtype=torch.float64, device=dev) for w in want}
         ptr = [out[w].data_ptr() if w in out else None for w in WANT]
         bound = C.c_uint64(0)
-        cap = 0 if max_pairs is None else int(max_pairs)
-        rc = lib.ma_op_pc_smooth(ref.data_ptr(), N, ref.shape[1], radius, (C.c_float * 3)(*origin.tolist()), float(cell), (C.c_int32 * 3)(*dims.tolist()),
-                                 int(min_count), cap, *ptr, C.byref(bound), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != _lib.MA_OK and bound.value > (cap or MAX_PAIRS):
-            raise ValueError(f"smooth_points: the pair bound {bound.value} exceeds max_pairs {cap or MAX_PAIRS} (N = {N}, radius {radius}): "
-                             "use a smaller radius or fewer points")
+        rc = lib.ma_op_pc_smooth(ref.data_ptr(), N, ref.shape[1], radius, *grid_args, int(min_count), cap, *ptr, C.byref(bound), ws.data_ptr(), nbytes,
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        check_pair_bound("smooth_points", rc, bound.value, cap, N, radius)
         _lib.check(rc)
     return {w: out[w] for w in WANT if w in want}
 
@@ -85,18 +69,6 @@ def check_smooth_args(radius, iters) -> tuple:
     if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= MAX_ITERS:
         raise ValueError(f"iters must be an integer in 1..{MAX_ITERS}, got {iters!r}")
     return radius, int(iters)
-
-
-def check_smooth_cloud(rows) -> np.ndarray:
-    """The checks of smooth_rows on the cloud that need no device; returns rows as an array."""
-    rows = np.asarray(rows)
-    if rows.ndim != 2 or rows.shape[1] < 3 or not np.issubdtype(rows.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {rows.shape} {rows.dtype}")
-    if not 1 <= rows.shape[0] <= MAX_POINTS:
-        raise ValueError(f"smoothing needs 1 <= N <= 2^22 points, got N = {rows.shape[0]}")
-    if not np.isfinite(rows[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
-    return rows
 
 
 def stayed(count, eigvals, min_count=DEFAULT_MIN_COUNT):
@@ -111,7 +83,7 @@ def smooth_rows(rows, radius, iters, uid: str, device="cuda") -> np.ndarray:
     last pass's normal, negated where its dot product with the file's normal is negative; where the last pass left the row in place
     they are kept.  Every other column is kept.  Prints the smoothing line of the command line."""
     radius, iters = check_smooth_args(radius, iters)
-    rows = check_smooth_cloud(rows)
+    rows = check_host_cloud(rows, "smoothing")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("smooth_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")

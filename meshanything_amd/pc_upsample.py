@@ -20,10 +20,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_cluster import MAX_PAIRS, MAX_RADIUS_IN_CELLS, _check_cloud, check_radius, choose_cluster_grid
+from .pc_cluster import (_check_cloud, check_host_cloud, check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid,
+                         grid_workspace)
 from .pc_normals import MAX_POINTS, _need_cuda
-from .pc_outliers import _check_grid
-from .pc_smooth import DEFAULT_MIN_COUNT, check_smooth_cloud, smooth_points, stayed
+from .pc_smooth import DEFAULT_MIN_COUNT, smooth_points, stayed
 
 MAX_M = 64                                                       # MA_PC_UPSAMPLE_MAX_M
 MAX_SLOTS = 1 << 31                                              # ma_op_pc_upsample: N * (2m+1)^2
@@ -68,12 +68,8 @@ def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, acti
         raise ValueError(f"N * (2m+1)^2 must be at most 2^31, got N = {N}, m = {m}")
     if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 0 <= int(capacity) <= MAX_POINTS):
         raise ValueError(f"capacity must be None or an integer in 0..2^22, got {capacity!r}")
-    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
-        raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
-    if grid is not None:
-        grid = _check_grid(grid)
-        if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
-            raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
+    cap = check_max_pairs(max_pairs)
+    grid = check_radius_grid(grid, radius)
     _need_cuda(points, "upsample_points")
     if normals.device != points.device or (active is not None and active.device != points.device):
         raise ValueError("points, normals and active must be on the same device")
@@ -83,29 +79,16 @@ def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, acti
         ref = points.contiguous()
         nrm = normals.contiguous()
         act = None if active is None else active.to(torch.uint8).contiguous()
-        if grid is None:
-            host = ref[:, :3].cpu().numpy()
-            if not np.isfinite(host).all():
-                raise ValueError("the point cloud has non-finite coordinates")
-            grid = choose_cluster_grid(host, radius)
-        origin, cell, dims = grid
-        nbytes = lib.ma_pc_upsample_workspace_bytes(N, int(dims[0]), int(dims[1]), int(dims[2]))
-        if nbytes == 0:
-            raise ValueError(f"outside the limits of ma_op_pc_upsample: N = {N}, dims = {dims.tolist()}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        grid_args, ws, nbytes = grid_workspace(lib, "upsample", ref, radius, grid)
         counts = torch.empty(N, dtype=torch.int32, device=dev)
         rows = 0 if count_only else (min(N * lattice_size(m), MAX_POINTS - N) if capacity is None else int(capacity))
         xyz = None if count_only else torch.empty((rows, 3), dtype=torch.float32, device=dev)
         seed = None if count_only else torch.empty(rows, dtype=torch.int32, device=dev)
         total, bound = C.c_uint64(0), C.c_uint64(0)
-        cap = 0 if max_pairs is None else int(max_pairs)
-        rc = lib.ma_op_pc_upsample(ref.data_ptr(), N, ref.shape[1], nrm.data_ptr(), None if act is None else act.data_ptr(), m, radius / m,
-                                   (C.c_float * 3)(*origin.tolist()), float(cell), (C.c_int32 * 3)(*dims.tolist()), cap, counts.data_ptr(),
-                                   None if count_only else xyz.data_ptr(), None if count_only else seed.data_ptr(), rows, C.byref(total), C.byref(bound),
-                                   ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != _lib.MA_OK and bound.value > (cap or MAX_PAIRS):
-            raise ValueError(f"upsample_points: the pair bound {bound.value} exceeds max_pairs {cap or MAX_PAIRS} (N = {N}, radius {radius}): "
-                             "use a smaller radius or fewer points")
+        rc = lib.ma_op_pc_upsample(ref.data_ptr(), N, ref.shape[1], nrm.data_ptr(), None if act is None else act.data_ptr(), m, radius / m, *grid_args, cap,
+                                   counts.data_ptr(), None if count_only else xyz.data_ptr(), None if count_only else seed.data_ptr(), rows,
+                                   C.byref(total), C.byref(bound), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        check_pair_bound("upsample_points", rc, bound.value, cap, N, radius)
         if rc != _lib.MA_OK and not count_only and total.value > min(rows, MAX_POINTS - N):
             raise ValueError(f"upsample_points: the total {total.value} exceeds {'2^22 - N' if total.value > MAX_POINTS - N else 'the capacity'} = "
                              f"{min(rows, MAX_POINTS - N)} (N = {N}, radius {radius}, m = {m}): use a smaller m or radius")
@@ -146,7 +129,7 @@ def upsample_rows(rows, radius, target, uid: str, device="cuda", return_fit=Fals
     come back unchanged.  Prints the upsampling line of the command line.  return_fit: also return the dict of the fit ("normals"
     (N, 3) float64, "active" (N) bool, "m", "seed" (T) int32)."""
     radius, target = check_upsample_args(radius, target)
-    rows = check_smooth_cloud(rows)
+    rows = check_host_cloud(rows, "smoothing")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("upsample_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
