@@ -66,6 +66,21 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
+# The input steps whose switch is a distance (0 = off), in the order their errors are reported: the switch, then the flags that need it as
+# {flag: (default, range test or None, the range's wording)}.  The fifth step's --outlier_k and --outlier_std follow another pattern, below.
+STEP_FLAGS = (
+    ("upsample_radius", {"upsample_points": (4 * 4096, lambda v: 4096 <= v <= 1 << 22, "in 4096..4194304")}),
+    ("smooth_radius", {"smooth_iters": (1, lambda v: 1 <= v <= 8, "in 1..8")}),
+    ("plane_threshold", {"plane_iters": (1024, lambda v: 1 <= v <= 65536, "in 1..65536"), "plane_count": (1, lambda v: 1 <= v <= 8, "in 1..8"),
+                         "plane_min_fraction": (0.2, lambda v: 0.0 < v <= 1.0, "in (0, 1]")}),
+    ("cluster_radius", {"cluster_mode": ("largest", None, None), "cluster_min_points": (4096, None, None)}),   # its two floors: after the table
+)
+
+
+def _listed(flags) -> str:
+    return flags[0] if len(flags) == 1 else ", ".join(flags[:-1]) + " and " + flags[-1]
+
+
 def get_args(argv=None):
     p = argparse.ArgumentParser("MeshAnything", add_help=True)
     p.add_argument("--llm", default="facebook/opt-350m", type=str)
@@ -126,52 +141,24 @@ def get_args(argv=None):
     p.add_argument("--upsample_points", default=None, type=int,
                    help="with --upsample_radius: upsample an input of fewer points to at least this many (4096..4194304, default 16384 = 4 x 4096)")
     args = p.parse_args(argv)
-    if not (0.0 <= args.upsample_radius < float("inf")):
-        p.error("--upsample_radius must be finite and >= 0 (0 = off)")
-    if args.input_type == "mesh" and (args.upsample_radius != 0 or args.upsample_points is not None):
-        p.error("--upsample_radius and --upsample_points apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
-    if args.upsample_radius == 0 and args.upsample_points is not None:
-        p.error("--upsample_points needs --upsample_radius > 0")
-    if args.upsample_points is not None and not 4096 <= args.upsample_points <= 1 << 22:
-        p.error("--upsample_points must be in 4096..4194304")
-    args.upsample_points = 4 * 4096 if args.upsample_points is None else args.upsample_points
-    if not (0.0 <= args.smooth_radius < float("inf")):
-        p.error("--smooth_radius must be finite and >= 0 (0 = off)")
-    if args.input_type == "mesh" and (args.smooth_radius != 0 or args.smooth_iters is not None):
-        p.error("--smooth_radius and --smooth_iters apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
-    if args.smooth_radius == 0 and args.smooth_iters is not None:
-        p.error("--smooth_iters needs --smooth_radius > 0")
-    if args.smooth_iters is not None and not 1 <= args.smooth_iters <= 8:
-        p.error("--smooth_iters must be in 1..8")
-    args.smooth_iters = 1 if args.smooth_iters is None else args.smooth_iters
-    if not (0.0 <= args.plane_threshold < float("inf")):
-        p.error("--plane_threshold must be finite and >= 0 (0 = off)")
-    others = args.plane_iters is not None or args.plane_count is not None or args.plane_min_fraction is not None
-    if args.input_type == "mesh" and (args.plane_threshold != 0 or others):
-        p.error("--plane_threshold, --plane_iters, --plane_count and --plane_min_fraction apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
-    if args.plane_threshold == 0 and others:
-        p.error("--plane_iters, --plane_count and --plane_min_fraction need --plane_threshold > 0")
-    if args.plane_iters is not None and not 1 <= args.plane_iters <= 65536:
-        p.error("--plane_iters must be in 1..65536")
-    if args.plane_count is not None and not 1 <= args.plane_count <= 8:
-        p.error("--plane_count must be in 1..8")
-    if args.plane_min_fraction is not None and not (0.0 < args.plane_min_fraction <= 1.0):
-        p.error("--plane_min_fraction must be in (0, 1]")
-    args.plane_iters = 1024 if args.plane_iters is None else args.plane_iters
-    args.plane_count = 1 if args.plane_count is None else args.plane_count
-    args.plane_min_fraction = 0.2 if args.plane_min_fraction is None else args.plane_min_fraction
-    if not (0.0 <= args.cluster_radius < float("inf")):
-        p.error("--cluster_radius must be finite and >= 0 (0 = off)")
-    if args.input_type == "mesh" and (args.cluster_radius != 0 or args.cluster_mode is not None or args.cluster_min_points is not None):
-        p.error("--cluster_radius, --cluster_mode and --cluster_min_points apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
-    if args.cluster_radius == 0 and (args.cluster_mode is not None or args.cluster_min_points is not None):
-        p.error("--cluster_mode and --cluster_min_points need --cluster_radius > 0")
-    if args.cluster_min_points is not None and args.upsample_radius > 0 and args.cluster_min_points < 64:
+    for switch, others in STEP_FLAGS:
+        flags = [f"--{name}" for name in (switch, *others)]
+        given = [getattr(args, name) is not None for name in others]
+        if not (0.0 <= getattr(args, switch) < float("inf")):
+            p.error(f"{flags[0]} must be finite and >= 0 (0 = off)")
+        if args.input_type == "mesh" and (getattr(args, switch) != 0 or any(given)):
+            p.error(f"{_listed(flags)} apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+        if getattr(args, switch) == 0 and any(given):
+            p.error(f"{_listed(flags[1:])} need{'s' if len(others) == 1 else ''} {flags[0]} > 0")
+        for name, (default, ok, wording) in others.items():
+            if getattr(args, name) is None:
+                setattr(args, name, default)
+            elif ok is not None and not ok(getattr(args, name)):
+                p.error(f"--{name} must be {wording}")
+    if args.upsample_radius > 0 and args.cluster_min_points < 64:            # the default passes both
         p.error("--cluster_min_points must be at least 64, the rows upsampling takes")
-    if args.cluster_min_points is not None and args.upsample_radius == 0 and args.cluster_min_points < 4096:
+    if args.upsample_radius == 0 and args.cluster_min_points < 4096:
         p.error("--cluster_min_points must be at least 4096, the rows the uniform draw needs")
-    args.cluster_mode = args.cluster_mode or "largest"
-    args.cluster_min_points = 4096 if args.cluster_min_points is None else args.cluster_min_points
     if args.outlier_k != 0 and not 3 <= args.outlier_k <= 32:
         p.error("--outlier_k must be 0 (off) or in 3..32")
     if not (0.0 <= args.outlier_std < float("inf")):
@@ -196,6 +183,7 @@ def get_args(argv=None):
 def main():
     from meshanything_amd import dp
     from meshanything_amd.checkpoint import load_safetensors_items, synthetic_items
+    from meshanything_amd.cloud_prep import CloudPrep
     from meshanything_amd.data import Dataset, uid_of
     from meshanything_amd.mesh_export import faces_from_coords, fix_normals, merge_meshes, write_obj
     from meshanything_amd.mesh_score import DEFAULT_MESH_SCALE
@@ -239,12 +227,7 @@ def main():
         pc_list, _ = process_mesh_to_pc(meshes, marching_cubes=True, device=sample_device)
         dataset = Dataset.from_clouds(pc_list, [uid_of(p) for p in input_list])
     else:
-        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, normal_k=args.normal_k, point_sampling=args.point_sampling,
-                          outlier_k=args.outlier_k, outlier_std=args.outlier_std, cluster_radius=args.cluster_radius, cluster_mode=args.cluster_mode,
-                          cluster_min_points=args.cluster_min_points, plane_threshold=args.plane_threshold, plane_iters=args.plane_iters,
-                          plane_count=args.plane_count, plane_min_fraction=args.plane_min_fraction, smooth_radius=args.smooth_radius,
-                          smooth_iters=args.smooth_iters, upsample_radius=args.upsample_radius,
-                          upsample_points=args.upsample_points if args.upsample_radius > 0 else None)
+        dataset = Dataset(args.input_type, input_list, args.mc, sample_device=sample_device, **vars(CloudPrep.from_args(args)))
 
     begin = time.time()
     print("Generation Start!!!")

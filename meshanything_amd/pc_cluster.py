@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_normals import MAX_POINTS, _need_cuda
-from .pc_outliers import MAX_DIM, _check_grid, choose_grid
+from .pc_common import MAX_DIM, check_device_cloud, check_grid, check_host_cloud, check_want, cuda_device, is_int, is_real, need_cuda
+from .pc_outliers import choose_grid
 
 MAX_PAIRS = 1 << 36                                              # MA_PC_CLUSTER_MAX_PAIRS
 MAX_RADIUS_IN_CELLS = 8                                          # ma_op_pc_cluster: radius / cell <= 8
@@ -28,7 +28,7 @@ MODES = ("largest", "split")
 
 
 def check_radius(radius) -> float:
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (0.0 < float(radius) < float("inf")):
+    if not is_real(radius) or not (0.0 < float(radius) < float("inf")):
         raise ValueError(f"radius must be finite and > 0, got {radius!r}")
     if not np.isfinite(np.float32(radius)) or not np.float32(radius) > 0:
         raise ValueError(f"radius must be a positive finite float32, got {radius!r}")
@@ -44,9 +44,6 @@ def choose_cluster_grid(xyz, radius):
     box at three cells an axis with cell = radius.  A box without extent: one cell.  A function of the array and the radius alone: no
     random numbers.  The grid only decides the time."""
     radius = check_radius(radius)
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or xyz.shape[0] < 1:
-        raise ValueError(f"a point cloud must be a (N, >= 3) array, got {xyz.shape}")
     r32 = np.float32(radius)
     if float(r32) < radius:
         r32 = np.nextafter(r32, np.float32(np.inf))
@@ -63,28 +60,19 @@ def choose_cluster_grid(xyz, radius):
         along -= 1
 
 
-def _check_cloud(points):
-    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] not in (3, 6):
-        raise ValueError(f"points must be a (N, 3) or (N, 6) tensor, got {tuple(points.shape) if hasattr(points, 'shape') else type(points).__name__}")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points must be float32, got {points.dtype}")
-    if not 1 <= points.shape[0] <= MAX_POINTS:
-        raise ValueError(f"need 1 <= N <= 2^22 points, got N = {points.shape[0]}")
-
-
 # ---- what every radius search over the grid shares (euclidean_clusters, pc_smooth.smooth_points, pc_upsample.upsample_points) ----------
 def check_max_pairs(max_pairs) -> int:
     """The check on max_pairs; returns the cap the library takes, 0 = its own."""
-    if max_pairs is not None and (isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= int(max_pairs) < 1 << 64):
+    if max_pairs is not None and (not is_int(max_pairs) or not 1 <= int(max_pairs) < 1 << 64):
         raise ValueError(f"max_pairs must be None or an integer in 1..2^64 - 1, got {max_pairs!r}")
     return 0 if max_pairs is None else int(max_pairs)
 
 
 def check_radius_grid(grid, radius):
-    """An explicit grid, checked as `pc_outliers._check_grid` does and against the ratio rule; None stays None."""
+    """An explicit grid, checked as `pc_common.check_grid` does and against the ratio rule; None stays None."""
     if grid is None:
         return None
-    grid = _check_grid(grid)
+    grid = check_grid(grid)
     if not radius / float(grid[1]) <= MAX_RADIUS_IN_CELLS:
         raise ValueError(f"the grid's cell must be at least radius / {MAX_RADIUS_IN_CELLS}, got cell {float(grid[1])} for radius {radius}")
     return grid
@@ -114,18 +102,6 @@ def check_pair_bound(fn: str, rc: int, bound: int, cap: int, N: int, radius: flo
                          "use a smaller radius or fewer points")
 
 
-def check_host_cloud(xyz, noun: str) -> np.ndarray:
-    """The checks of split_rows, smooth_rows and upsample_rows on the cloud that need no device; returns xyz as an array."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
-    if not 1 <= xyz.shape[0] <= MAX_POINTS:
-        raise ValueError(f"{noun} needs 1 <= N <= 2^22 points, got N = {xyz.shape[0]}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
-    return xyz
-
-
 def euclidean_clusters(points: torch.Tensor, radius, grid=None, want=("labels",), max_pairs=None):
     """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns, finite -> a dict with the entries named in `want`: "labels"
     (N) int32, labels[i] = the smallest row index in the connected component of i, rows i and j being linked iff
@@ -134,13 +110,11 @@ def euclidean_clusters(points: torch.Tensor, radius, grid=None, want=("labels",)
     points (copied to the host for it); the result does not depend on it.  max_pairs: the cap on the pair bound the library computes
     before it searches (None = its own, 2^36); a bound above it is a ValueError that names both."""
     radius = check_radius(radius)
-    _check_cloud(points)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in WANT for w in want):
-        raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
+    check_device_cloud(points, 1)
+    want = check_want(want, WANT)
     cap = check_max_pairs(max_pairs)
     grid = check_radius_grid(grid, radius)
-    _need_cuda(points, "euclidean_clusters")
+    need_cuda(points, "euclidean_clusters")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -171,7 +145,7 @@ def components(labels):
 def check_split_args(radius, min_points, mode) -> tuple:
     """The checks on (radius, min_points, mode); returns them as (float, int, str)."""
     radius = check_radius(radius)
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or int(min_points) < 1:
+    if not is_int(min_points) or int(min_points) < 1:
         raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
@@ -185,9 +159,7 @@ def split_rows(xyz, radius, min_points, mode, uid: str, device="cuda"):
     min_points rows is a ValueError that names the largest size."""
     radius, min_points, mode = check_split_args(radius, min_points, mode)
     xyz = check_host_cloud(xyz, "clustering")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("split_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "split_rows")
     host = np.ascontiguousarray(xyz[:, :3], dtype=np.float32)
     grid = choose_cluster_grid(host, radius)
     with torch.cuda.device(dev):

@@ -15,26 +15,23 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pc_common import MAX_POINTS, as_host_cloud, check_device_cloud, check_finite, cuda_device, is_int, need_cuda, upload_xyz
 
-MAX_POINTS, MAX_PICKS, ONE_MAX_POINTS = 1 << 22, 1 << 16, 1 << 14   # MA_PC_FPS_MAX_POINTS, _MAX_PICKS, _ONE_MAX_POINTS
+MAX_PICKS, ONE_MAX_POINTS = 1 << 16, 1 << 14                        # MA_PC_FPS_MAX_PICKS, _ONE_MAX_POINTS
 FORM_AUTO, FORM_ONE, FORM_MANY = 0, 1, 2
-
-
-def _is_int(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
 
 
 def check_fps_args(N: int, n, start, form) -> tuple:
     """The checks on (n, start, form) for a cloud of N rows; returns them as ints, start = -1 for None."""
-    if not _is_int(n) or not 1 <= int(n) <= MAX_PICKS:
+    if not is_int(n) or not 1 <= int(n) <= MAX_PICKS:
         raise ValueError(f"n must be an integer in 1..2^16, got {n!r}")
     if not int(n) <= N <= MAX_POINTS:
         raise ValueError(f"need n <= N <= 2^22 points, got N = {N} with n = {n}")
     if start is None:
         start = -1
-    elif not _is_int(start) or not 0 <= int(start) < N:
+    elif not is_int(start) or not 0 <= int(start) < N:
         raise ValueError(f"start must be None or a row in [0, {N}), got {start!r}")
-    if not _is_int(form) or int(form) not in (FORM_AUTO, FORM_ONE, FORM_MANY):
+    if not is_int(form) or int(form) not in (FORM_AUTO, FORM_ONE, FORM_MANY):
         raise ValueError(f"form must be 0 (automatic), 1 (one workgroup) or 2 (many workgroups), got {form!r}")
     if int(form) == FORM_ONE and N > ONE_MAX_POINTS:
         raise ValueError(f"form 1 (one workgroup) holds at most {ONE_MAX_POINTS} points, got N = {N}")
@@ -47,14 +44,10 @@ def farthest_point_sample(points: torch.Tensor, n: int, start=None, form: int = 
     within sqrt(d2[n - 1]) of a picked one, up to the last pick's own update).  start: the first row, None = the row farthest from the
     bounding box's centre.  form: 0 = the library's choice, 1 = one workgroup (N <= 16 384), 2 = many workgroups; the result does not
     depend on it (ma_op_pc_fps)."""
-    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] not in (3, 6):
-        raise ValueError(f"points must be a (N, 3) or (N, 6) tensor, got {tuple(points.shape) if hasattr(points, 'shape') else type(points).__name__}")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points must be float32, got {points.dtype}")
+    check_device_cloud(points)
     N = points.shape[0]
     n, start, form = check_fps_args(N, n, start, form)
-    if points.device.type != "cuda":
-        raise ValueError("farthest_point_sample runs on the GPU: points must be a CUDA tensor (there is no CPU fallback)")
+    need_cuda(points, "farthest_point_sample")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -72,17 +65,14 @@ def farthest_point_sample(points: torch.Tensor, n: int, start=None, form: int = 
 
 def check_cloud_for_fps(xyz, n_points: int) -> np.ndarray:
     """The checks of the fps branches that need no device: a floating (N, >= 3) array, n_points <= N <= 2^22, finite xyz."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
+    xyz = as_host_cloud(xyz)
     if xyz.shape[0] < n_points:
         raise ValueError(f"farthest-point sampling keeps {n_points} points: the input should have at least as many, got {xyz.shape[0]}")
     if xyz.shape[0] > MAX_POINTS:
         raise ValueError(f"farthest-point sampling takes at most 2^22 points, got {xyz.shape[0]}")
     if not 1 <= n_points <= MAX_PICKS:
         raise ValueError(f"farthest-point sampling keeps at most 2^16 points, got n_points = {n_points}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
+    check_finite(xyz)
     return xyz
 
 
@@ -90,10 +80,7 @@ def fps_rows(xyz, n_points: int, device="cuda") -> np.ndarray:
     """xyz (N, >= 3) host array -> the n_points rows farthest-point sampling keeps, in pick order (int64): the first three columns are
     uploaded as float32 and sampled with the automatic start and form.  Consumes no random numbers."""
     xyz = check_cloud_for_fps(xyz, n_points)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("farthest-point sampling runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "farthest-point sampling")
     with torch.cuda.device(dev):
-        cloud = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], dtype=np.float32)).to(dev)
-        idx, _ = farthest_point_sample(cloud, n_points)
+        idx, _ = farthest_point_sample(upload_xyz(xyz, dev), n_points)
         return idx.cpu().numpy().astype(np.int64)

@@ -16,37 +16,23 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pc_common import MAX_POINTS, MAX_QUERIES, as_host_cloud, check_device_cloud, check_finite, cuda_device, need_cuda, upload_xyz
 
-MIN_K, MAX_K = 3, 32                                             # MA_PC_KNN_MIN_K, MA_PC_KNN_MAX_K
-MAX_POINTS, MAX_QUERIES, MAX_SPLITS = 1 << 22, 1 << 20, 64       # MA_PC_KNN_MAX_POINTS, _MAX_QUERIES, _MAX_SPLITS
+MIN_K, MAX_K, MAX_SPLITS = 3, 32, 64                             # MA_PC_KNN_MIN_K, _MAX_K, _MAX_SPLITS
 
 
-def _check_k(k) -> int:
+def check_k(k) -> int:
     if isinstance(k, bool) or int(k) != k or not MIN_K <= int(k) <= MAX_K:
         raise ValueError(f"k must be an integer in {MIN_K}..{MAX_K}, got {k!r}")
     return int(k)
-
-
-def _check_points(points, k: int):
-    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] not in (3, 6):
-        raise ValueError(f"points must be a (N, 3) or (N, 6) tensor, got {tuple(points.shape) if hasattr(points, 'shape') else type(points).__name__}")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points must be float32, got {points.dtype}")
-    if not k <= points.shape[0] <= MAX_POINTS:
-        raise ValueError(f"need k <= N <= 2^22 points, got N = {points.shape[0]} with k = {k}")
-
-
-def _need_cuda(t, what: str):
-    if t.device.type != "cuda":
-        raise ValueError(f"{what} runs on the GPU: points must be a CUDA tensor (there is no CPU fallback)")
 
 
 def knn(points: torch.Tensor, query_idx=None, k: int = 16, splits: int = 0):
     """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns; query_idx (Q) integer rows of points, None = every row ->
     (nbr_idx (Q, k) int32, nbr_d2 (Q, k) float32), nearest first, ordered by (squared distance, index) (ma_op_pc_knn).  splits: the
     number of chunks the reference range is searched in, 0 = the library's choice; the result does not depend on it."""
-    k = _check_k(k)
-    _check_points(points, k)
+    k = check_k(k)
+    check_device_cloud(points, k, "k")
     if isinstance(splits, bool) or int(splits) != splits or not 0 <= int(splits) <= MAX_SPLITS:
         raise ValueError(f"splits must be an integer in 0..{MAX_SPLITS}, got {splits!r}")
     N = points.shape[0]
@@ -56,7 +42,7 @@ def knn(points: torch.Tensor, query_idx=None, k: int = 16, splits: int = 0):
             raise ValueError(f"query_idx must be a (Q) int32 or int64 tensor with 1 <= Q <= 2^20, got {tuple(query_idx.shape)} {query_idx.dtype}")
     elif N > MAX_QUERIES:
         raise ValueError(f"without query_idx every point is a query: N = {N} exceeds 2^20 queries")
-    _need_cuda(points, "knn")
+    need_cuda(points, "knn")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -85,9 +71,9 @@ def estimate_normals(points: torch.Tensor, nbr_idx: torch.Tensor):
     of largest magnitude positive (ma_op_pc_normals).  Unoriented: `orient_normals` decides the signs."""
     if not torch.is_tensor(nbr_idx) or nbr_idx.dim() != 2 or nbr_idx.dtype != torch.int32 or not 1 <= nbr_idx.shape[0] <= MAX_QUERIES:
         raise ValueError("nbr_idx must be a (Q, k) int32 tensor with 1 <= Q <= 2^20")
-    k = _check_k(nbr_idx.shape[1])
-    _check_points(points, k)
-    _need_cuda(points, "estimate_normals")
+    k = check_k(nbr_idx.shape[1])
+    check_device_cloud(points, k, "k")
+    need_cuda(points, "estimate_normals")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -151,10 +137,8 @@ def orient_normals(points, normals, nbr_idx) -> np.ndarray:
 
 def check_xyz(xyz, n_points: int, k: int) -> np.ndarray:
     """The checks of xyz_to_pc_normal that need no device; returns xyz as an array."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
-    k = _check_k(k)
+    xyz = as_host_cloud(xyz)
+    k = check_k(k)
     if n_points < k:
         raise ValueError(f"n_points = {n_points} is less than k = {k}")
     if xyz.shape[0] < n_points:
@@ -163,8 +147,7 @@ def check_xyz(xyz, n_points: int, k: int) -> np.ndarray:
         raise ValueError(f"a pc_xyz input may have at most 2^22 points, got {xyz.shape[0]}")
     if n_points > MAX_QUERIES:
         raise ValueError(f"n_points may be at most 2^20, got {n_points}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
+    check_finite(xyz)
     return xyz
 
 
@@ -180,16 +163,14 @@ def xyz_to_pc_normal(xyz, n_points: int = 4096, k: int = 16, device="cuda", samp
     xyz = check_xyz(xyz, n_points, k)
     if sampling not in ("random", "fps"):
         raise ValueError(f'sampling must be "random" or "fps", got {sampling!r}')
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("xyz_to_pc_normal runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "xyz_to_pc_normal")
     if sampling == "fps":
         from .pc_fps import check_fps_args, farthest_point_sample
         check_fps_args(xyz.shape[0], n_points, None, 0)
     else:
         idx = np.random.choice(xyz.shape[0], n_points, replace=False)
     with torch.cuda.device(dev):
-        cloud = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], dtype=np.float32)).to(dev)
+        cloud = upload_xyz(xyz, dev)
         if sampling == "fps":
             rows = farthest_point_sample(cloud, n_points)[0]
             idx = rows.cpu().numpy().astype(np.int64)

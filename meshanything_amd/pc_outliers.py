@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_normals import MAX_POINTS, MAX_QUERIES, _check_k, _check_points, _need_cuda, knn
+from .pc_common import (MAX_DIM, MAX_POINTS, MAX_QUERIES, as_host_cloud, check_device_cloud, check_finite, check_grid, check_want, cuda_device, is_int,
+                        is_real, need_cuda, upload_xyz)
+from .pc_normals import check_k, knn
 
-MAX_DIM, MAX_CELLS = 128, 1 << 21                                # MA_PC_GRID_MAX_DIM, MA_PC_GRID_MAX_CELLS
 GRID_SAMPLE = 1 << 16                                            # rows choose_grid looks at, at the most
 FORM_AUTO, FORM_BRUTE, FORM_GRID = 0, 1, 2
 GRID_FROM_N = 1 << 18                                            # form 0: the grid from this many points on
@@ -37,7 +38,7 @@ def choose_grid(xyz, k: int = 16, along=None):
     xyz = np.asarray(xyz)
     if xyz.ndim != 2 or xyz.shape[1] < 3 or xyz.shape[0] < 1:
         raise ValueError(f"a point cloud must be a (N, >= 3) array, got {xyz.shape}")
-    _check_k(k)
+    check_k(k)
     N = xyz.shape[0]
     sub = np.asarray(xyz[::max(1, -(-N // GRID_SAMPLE)), :3], dtype=np.float64)
     lo, hi = np.percentile(sub, 1.0, axis=0), np.percentile(sub, 99.0, axis=0)
@@ -52,37 +53,18 @@ def choose_grid(xyz, k: int = 16, along=None):
     return origin, cell, dims
 
 
-def _check_grid(grid):
-    try:
-        origin, cell, dims = grid
-        origin = np.asarray(origin, dtype=np.float32).reshape(-1)
-        dims_in = np.asarray(dims).reshape(-1)
-        cell = np.float32(cell)
-    except (TypeError, ValueError):
-        raise ValueError("grid must be (origin (3), cell, dims (3))") from None
-    if origin.shape != (3,) or dims_in.shape != (3,) or not np.issubdtype(dims_in.dtype, np.integer):
-        raise ValueError("grid must be (origin (3) floats, cell, dims (3) integers)")
-    if not np.isfinite(origin).all() or not (np.isfinite(cell) and cell > 0):
-        raise ValueError(f"the grid's origin must be finite and its cell finite and > 0, got {origin.tolist()} and {float(cell)}")
-    if (dims_in < 1).any() or (dims_in > MAX_DIM).any() or int(np.prod(dims_in.astype(np.int64))) > MAX_CELLS:
-        raise ValueError(f"the grid's dims must each lie in 1..{MAX_DIM} with a product of at most 2^21, got {dims_in.tolist()}")
-    return origin, cell, dims_in.astype(np.int32)
-
-
 def grid_knn(points: torch.Tensor, k: int = 16, grid=None, want=("idx", "d2")):
     """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns; every row is a query -> a dict with the entries named in
     `want`: "idx" (N, k) int32 and "d2" (N, k) float32, the lists `pc_normals.knn(points, None, k)` returns, bit for bit, and "mean"
     (N) float64, the mean of sqrt(d2) over each list (ma_op_pc_knn_grid).  With want = ("mean",) the lists are never written to
     memory.  grid: (origin, cell, dims), None = `choose_grid` of the points (copied to the host for it); the result does not depend on
     it.  Unlike `knn`, N may reach 2^22."""
-    k = _check_k(k)
-    _check_points(points, k)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in WANT for w in want):
-        raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
+    k = check_k(k)
+    check_device_cloud(points, k, "k")
+    want = check_want(want, WANT)
     if grid is not None:
-        grid = _check_grid(grid)
-    _need_cuda(points, "grid_knn")
+        grid = check_grid(grid)
+    need_cuda(points, "grid_knn")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -107,7 +89,7 @@ def grid_knn(points: torch.Tensor, k: int = 16, grid=None, want=("idx", "d2")):
 
 
 def _check_form(form) -> int:
-    if isinstance(form, bool) or not isinstance(form, (int, np.integer)) or int(form) not in (FORM_AUTO, FORM_BRUTE, FORM_GRID):
+    if not is_int(form) or int(form) not in (FORM_AUTO, FORM_BRUTE, FORM_GRID):
         raise ValueError(f"form must be 0 (automatic), 1 (brute force) or 2 (cell grid), got {form!r}")
     return int(form)
 
@@ -125,12 +107,12 @@ def knn_mean_distance(points: torch.Tensor, k: int = 16, form: int = 0) -> torch
     included at distance 0: (sum_j sqrt((double) d2_j)) / k in list order.  form: 1 = the brute force (`pc_normals.knn` and the same
     sum, N <= 2^20), 2 = the cell grid (`grid_knn`, N <= 2^22), 0 = a function of N alone.  The values do not depend on it, bit for
     bit."""
-    k = _check_k(k)
-    _check_points(points, k)
+    k = check_k(k)
+    check_device_cloud(points, k, "k")
     form = resolve_form(points.shape[0], _check_form(form))
     if form == FORM_BRUTE and points.shape[0] > MAX_QUERIES:
         raise ValueError(f"form 1 (brute force) takes at most 2^20 points, got N = {points.shape[0]}")
-    _need_cuda(points, "knn_mean_distance")
+    need_cuda(points, "knn_mean_distance")
     if form == FORM_GRID:
         return grid_knn(points, k, None, want=("mean",))["mean"]
     _, d2 = knn(points, None, k)
@@ -142,24 +124,21 @@ def knn_mean_distance(points: torch.Tensor, k: int = 16, form: int = 0) -> torch
 
 def check_filter_args(k, std_ratio, form=0) -> tuple:
     """The checks on (k, std_ratio, form); returns them as (int, float, int)."""
-    k = _check_k(k)
-    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float, np.integer, np.floating)) or not (0.0 <= float(std_ratio) < float("inf")):
+    k = check_k(k)
+    if not is_real(std_ratio) or not (0.0 <= float(std_ratio) < float("inf")):
         raise ValueError(f"std_ratio must be finite and >= 0, got {std_ratio!r}")
     return k, float(std_ratio), _check_form(form)
 
 
 def check_outlier_args(xyz, k, std_ratio, form=0) -> np.ndarray:
     """The checks of remove_statistical_outliers that need no device; returns xyz as an array."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
+    xyz = as_host_cloud(xyz)
     k, _, form = check_filter_args(k, std_ratio, form)
     if not k <= xyz.shape[0] <= MAX_POINTS:
         raise ValueError(f"outlier removal needs k <= N <= 2^22 points, got N = {xyz.shape[0]} with k = {k}")
     if form == FORM_BRUTE and xyz.shape[0] > MAX_QUERIES:
         raise ValueError(f"form 1 (brute force) takes at most 2^20 points, got N = {xyz.shape[0]}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
+    check_finite(xyz)
     return xyz
 
 
@@ -168,12 +147,9 @@ def remove_statistical_outliers(xyz, k: int = 16, std_ratio: float = 2.0, device
     threshold): mean_dist from `knn_mean_distance` on the GPU, then on the host threshold = mean_dist.mean() + std_ratio *
     mean_dist.std() (numpy float64, population sigma) and keep = mean_dist <= threshold."""
     xyz = check_outlier_args(xyz, k, std_ratio, form)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("remove_statistical_outliers runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "remove_statistical_outliers")
     with torch.cuda.device(dev):
-        cloud = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], dtype=np.float32)).to(dev)
-        m = knn_mean_distance(cloud, int(k), int(form)).cpu().numpy()
+        m = knn_mean_distance(upload_xyz(xyz, dev), int(k), int(form)).cpu().numpy()
     threshold = float(m.mean() + float(std_ratio) * m.std())
     return m <= threshold, m, threshold
 

@@ -17,9 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_normals import _need_cuda
+from .pc_common import MAX_POINTS, check_device_cloud, check_host_cloud, check_int, check_want, cuda_device, is_real, need_cuda, upload_xyz
 
-MAX_POINTS = 1 << 22                                             # MA_PC_PLANE_MAX_POINTS
 MAX_HYPOTHESES = 1 << 16                                         # MA_PC_PLANE_MAX_HYPOTHESES
 MAX_COUNT = 8                                                    # planes removed from one cloud
 SCORE_WANT = ("planes", "counts", "best")
@@ -28,27 +27,11 @@ SEED = 0x706c616e65                                              # "plane"
 
 
 def check_threshold(threshold) -> float:
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not (0.0 < float(threshold) < float("inf")):
+    if not is_real(threshold) or not (0.0 < float(threshold) < float("inf")):
         raise ValueError(f"threshold must be finite and > 0, got {threshold!r}")
     if not np.isfinite(np.float32(threshold)) or not np.float32(threshold) > 0:
         raise ValueError(f"threshold must be a positive finite float32, got {threshold!r}")
     return float(threshold)
-
-
-def _check_cloud(points):
-    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] not in (3, 6):
-        raise ValueError(f"points must be a (N, 3) or (N, 6) tensor, got {tuple(points.shape) if hasattr(points, 'shape') else type(points).__name__}")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points must be float32, got {points.dtype}")
-    if not 3 <= points.shape[0] <= MAX_POINTS:
-        raise ValueError(f"need 3 <= N <= 2^22 points, got N = {points.shape[0]}")
-
-
-def _check_want(want, names):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in names for w in want):
-        raise ValueError(f"want must name at least one of {names}, got {want!r}")
-    return want
 
 
 def score_planes(points: torch.Tensor, triples: torch.Tensor, threshold, want=("counts", "best")):
@@ -59,14 +42,14 @@ def score_planes(points: torch.Tensor, triples: torch.Tensor, threshold, want=("
     hypothesis of the greatest count, the lowest index among equals, -1 if all are degenerate.  Equal to the numpy restatement and to a
     second run, bit for bit."""
     threshold = check_threshold(threshold)
-    _check_cloud(points)
-    want = _check_want(want, SCORE_WANT)
+    check_device_cloud(points, 3)
+    want = check_want(want, SCORE_WANT)
     if not torch.is_tensor(triples) or triples.dim() != 2 or triples.shape[1] != 3 or triples.dtype != torch.int32:
         raise ValueError(f"triples must be a (H, 3) int32 tensor, got {tuple(triples.shape) if hasattr(triples, 'shape') else type(triples).__name__}"
                          f" {getattr(triples, 'dtype', '')}")
     if not 1 <= triples.shape[0] <= MAX_HYPOTHESES:
         raise ValueError(f"need 1 <= H <= 2^16 hypotheses, got H = {triples.shape[0]}")
-    _need_cuda(points, "score_planes")
+    need_cuda(points, "score_planes")
     if triples.device != points.device:
         raise ValueError(f"score_planes runs on the GPU: triples must be on the points' device {points.device}, got {triples.device}")
     lib = _lib.load()
@@ -101,10 +84,10 @@ def apply_plane(points: torch.Tensor, plane, threshold, want=("mask",)):
     "moments" (10) float64 over the inliers with q = p - a in float64: n, the sums of q and of the six products q qT (xx, xy, xz, yy, yz,
     zz), from a reduction of fixed shape: the same bits on every run, within n * 2^-52 * sum|term| of any other summation order."""
     threshold = check_threshold(threshold)
-    _check_cloud(points)
-    want = _check_want(want, APPLY_WANT)
+    check_device_cloud(points, 3)
+    want = check_want(want, APPLY_WANT)
     plane = _check_plane(plane)
-    _need_cuda(points, "apply_plane")
+    need_cuda(points, "apply_plane")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -126,8 +109,7 @@ def draw_triples(N: int, iters: int, round: int) -> np.ndarray:
     """(iters, 3) int32 rows in [0, N), from a generator of its own seeded with (SEED, round): the global numpy RNG is not touched, so the
     uniform draw of `Dataset` that follows sees the state it would have seen.  Repeated indices are allowed; they score as degenerate."""
     for name, v, lo, hi in (("N", N, 1, MAX_POINTS), ("iters", iters, 1, MAX_HYPOTHESES), ("round", round, 0, 1 << 31)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        check_int(name, v, lo, hi)
     return np.random.Generator(np.random.PCG64([SEED, int(round)])).integers(0, int(N), (int(iters), 3)).astype(np.int32)
 
 
@@ -150,24 +132,11 @@ def fit_plane(moments, a):
 def check_remove_args(threshold, iters, count, min_fraction) -> tuple:
     """The checks on (threshold, iters, count, min_fraction); returns them as (float, int, int, float)."""
     threshold = check_threshold(threshold)
-    for name, v, hi in (("iters", iters, MAX_HYPOTHESES), ("count", count, MAX_COUNT)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
-            raise ValueError(f"{name} must be an integer in 1..{hi}, got {v!r}")
-    if isinstance(min_fraction, bool) or not isinstance(min_fraction, (int, float, np.integer, np.floating)) or not 0.0 < float(min_fraction) <= 1.0:
+    check_int("iters", iters, 1, MAX_HYPOTHESES)
+    check_int("count", count, 1, MAX_COUNT)
+    if not is_real(min_fraction) or not 0.0 < float(min_fraction) <= 1.0:
         raise ValueError(f"min_fraction must be in (0, 1], got {min_fraction!r}")
     return threshold, int(iters), int(count), float(min_fraction)
-
-
-def check_plane_cloud(xyz) -> np.ndarray:
-    """The checks of remove_planes on the cloud that need no device; returns xyz as an array."""
-    xyz = np.asarray(xyz)
-    if xyz.ndim != 2 or xyz.shape[1] < 3 or not np.issubdtype(xyz.dtype, np.floating):
-        raise ValueError(f"a point cloud must be a floating (N, >= 3) array, got {xyz.shape} {xyz.dtype}")
-    if not 3 <= xyz.shape[0] <= MAX_POINTS:
-        raise ValueError(f"plane removal needs 3 <= N <= 2^22 points, got N = {xyz.shape[0]}")
-    if not np.isfinite(xyz[:, :3]).all():
-        raise ValueError("the point cloud has non-finite coordinates")
-    return xyz
 
 
 def remove_planes(xyz, threshold, iters, count, min_fraction, n_points, uid: str, device="cuda"):
@@ -178,15 +147,13 @@ def remove_planes(xyz, threshold, iters, count, min_fraction, n_points, uid: str
     its inliers.  Prints the plane line of the command line.  Fewer than n_points rows left is a ValueError naming the uid and the
     number."""
     threshold, iters, count, min_fraction = check_remove_args(threshold, iters, count, min_fraction)
-    xyz = check_plane_cloud(xyz)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("remove_planes runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    xyz = check_host_cloud(xyz, "plane removal", 3)
+    dev = cuda_device(device, "remove_planes")
     N = xyz.shape[0]
     kept = np.arange(N, dtype=np.int64)
     found, stopped = [], None
     with torch.cuda.device(dev):
-        pts = torch.from_numpy(np.ascontiguousarray(xyz[:, :3], dtype=np.float32)).to(dev)
+        pts = upload_xyz(xyz, dev)
         for r in range(count):
             rows = pts.shape[0]
             if rows < 3:

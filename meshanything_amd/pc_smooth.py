@@ -17,9 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_cluster import (_check_cloud, check_host_cloud, check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid,
-                         grid_workspace)
-from .pc_normals import _need_cuda
+from .pc_cluster import check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid, grid_workspace
+from .pc_common import check_device_cloud, check_host_cloud, check_int, check_want, cuda_device, is_int, need_cuda
 
 MIN_COUNT = 3                                                    # MA_PC_SMOOTH_MIN_COUNT: the points a plane takes
 DEFAULT_MIN_COUNT = 6
@@ -38,15 +37,13 @@ def smooth_points(points: torch.Tensor, radius, min_count=DEFAULT_MIN_COUNT, gri
     the cap on the pair bound the library computes before it searches (None = its own, 2^36); a bound above it is a ValueError that
     names both."""
     radius = check_radius(radius)
-    _check_cloud(points)
-    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not MIN_COUNT <= int(min_count) < 1 << 31:
+    check_device_cloud(points, 1)
+    if not is_int(min_count) or not MIN_COUNT <= int(min_count) < 1 << 31:
         raise ValueError(f"min_count must be an integer >= {MIN_COUNT}, got {min_count!r}")
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in WANT for w in want):
-        raise ValueError(f"want must name at least one of {WANT}, got {want!r}")
+    want = check_want(want, WANT)
     cap = check_max_pairs(max_pairs)
     grid = check_radius_grid(grid, radius)
-    _need_cuda(points, "smooth_points")
+    need_cuda(points, "smooth_points")
     lib = _lib.load()
     dev = points.device
     with torch.cuda.device(dev):
@@ -66,9 +63,7 @@ def smooth_points(points: torch.Tensor, radius, min_count=DEFAULT_MIN_COUNT, gri
 def check_smooth_args(radius, iters) -> tuple:
     """The checks on (radius, iters); returns them as (float, int)."""
     radius = check_radius(radius)
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= MAX_ITERS:
-        raise ValueError(f"iters must be an integer in 1..{MAX_ITERS}, got {iters!r}")
-    return radius, int(iters)
+    return radius, check_int("iters", iters, 1, MAX_ITERS)
 
 
 def stayed(count, eigvals, min_count=DEFAULT_MIN_COUNT):
@@ -84,9 +79,7 @@ def smooth_rows(rows, radius, iters, uid: str, device="cuda") -> np.ndarray:
     they are kept.  Every other column is kept.  Prints the smoothing line of the command line."""
     radius, iters = check_smooth_args(radius, iters)
     rows = check_host_cloud(rows, "smoothing")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("smooth_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "smooth_rows")
     host = np.ascontiguousarray(rows[:, :3], dtype=np.float32)
     grid = choose_cluster_grid(host, radius)
     with torch.cuda.device(dev):

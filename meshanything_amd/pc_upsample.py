@@ -20,9 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pc_cluster import (_check_cloud, check_host_cloud, check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid,
-                         grid_workspace)
-from .pc_normals import MAX_POINTS, _need_cuda
+from .pc_cluster import check_max_pairs, check_pair_bound, check_radius, check_radius_grid, choose_cluster_grid, grid_workspace
+from .pc_common import MAX_POINTS, check_device_cloud, check_host_cloud, check_int, cuda_device, is_int, need_cuda
 from .pc_smooth import DEFAULT_MIN_COUNT, smooth_points, stayed
 
 MAX_M = 64                                                       # MA_PC_UPSAMPLE_MAX_M
@@ -39,12 +38,6 @@ def lattice_size(m: int) -> int:
     return int((a[:, None] ** 2 + a[None, :] ** 2 <= m * m).sum()) - 1
 
 
-def _check_m(m) -> int:
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= MAX_M:
-        raise ValueError(f"m must be an integer in 1..{MAX_M}, got {m!r}")
-    return int(m)
-
-
 def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, active=None, grid=None, count_only=False, capacity=None, max_pairs=None):
     """points (N, 3 | 6) float32 on the GPU, xyz in the first three columns; normals (N, 3) float64 on the same GPU, a unit normal per
     row; active (N) bool or uint8 on the same GPU, or None = every row -> a dict: "xyz" (T, 3) float32, the lattice points at spacing
@@ -55,8 +48,8 @@ def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, acti
     output depends on it.  capacity: the rows to allocate for the output, None = min(N * lattice_size(m), 2^22 - N); a total above it,
     or above 2^22 - N, is a ValueError.  max_pairs: as in `smooth_points`."""
     radius = check_radius(radius)
-    m = _check_m(m)
-    _check_cloud(points)
+    m = check_int("m", m, 1, MAX_M)
+    check_device_cloud(points, 1)
     N = points.shape[0]
     if not torch.is_tensor(normals) or normals.dtype != torch.float64 or tuple(normals.shape) != (N, 3):
         raise ValueError(f"normals must be a float64 ({N}, 3) tensor, got "
@@ -66,11 +59,11 @@ def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, acti
                          f"{(tuple(active.shape), active.dtype) if torch.is_tensor(active) else type(active).__name__}")
     if N * (2 * m + 1) ** 2 > MAX_SLOTS:
         raise ValueError(f"N * (2m+1)^2 must be at most 2^31, got N = {N}, m = {m}")
-    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 0 <= int(capacity) <= MAX_POINTS):
+    if capacity is not None and (not is_int(capacity) or not 0 <= int(capacity) <= MAX_POINTS):
         raise ValueError(f"capacity must be None or an integer in 0..2^22, got {capacity!r}")
     cap = check_max_pairs(max_pairs)
     grid = check_radius_grid(grid, radius)
-    _need_cuda(points, "upsample_points")
+    need_cuda(points, "upsample_points")
     if normals.device != points.device or (active is not None and active.device != points.device):
         raise ValueError("points, normals and active must be on the same device")
     lib = _lib.load()
@@ -100,7 +93,7 @@ def upsample_points(points: torch.Tensor, normals: torch.Tensor, radius, m, acti
 def check_upsample_args(radius, target, n_points: int = N_POINTS) -> tuple:
     """The checks on (radius, target); returns them as (float, int)."""
     radius = check_radius(radius)
-    if isinstance(target, bool) or not isinstance(target, (int, np.integer)) or not n_points <= int(target) <= MAX_POINTS:
+    if not is_int(target) or not n_points <= int(target) <= MAX_POINTS:
         raise ValueError(f"the upsampling target must be an integer in {n_points}..2^22, got {target!r}")
     return radius, int(target)
 
@@ -130,9 +123,7 @@ def upsample_rows(rows, radius, target, uid: str, device="cuda", return_fit=Fals
     (N, 3) float64, "active" (N) bool, "m", "seed" (T) int32)."""
     radius, target = check_upsample_args(radius, target)
     rows = check_host_cloud(rows, "smoothing")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("upsample_rows runs on the GPU: device must be a CUDA device (there is no CPU fallback)")
+    dev = cuda_device(device, "upsample_rows")
     N = rows.shape[0]
     if N >= target:
         print(f"{uid}: upsampling (radius {radius:g}) not needed: {N} rows, at least the {target} asked for")

@@ -1,7 +1,8 @@
 """Upsampling of sparse input clouds on the MI355X (csrc/pc_upsample.hpp, meshanything_amd/pc_upsample.py): xyz, seed and counts against
 the brute-force restatement `pc_upsample_ref.upsample_ref`, over the grids of every case; the sphere's geometry; non-finite input, the
 capacity and the pair bound through the raw ABI; `upsample_rows`; through `Dataset(..., upsample_radius=...)` and through
-`main.py --upsample_radius`.  Every GPU step runs in a fresh interpreter under a time limit; the comparisons run here.
+`main.py --upsample_radius`; and, upsampling being the last of them, `Dataset` with every step of the input side on against the public
+functions composed by hand.  Every GPU step runs in a fresh interpreter under a time limit; the comparisons run here.
 
 Every comparison of the op is EXACT, order included: the normals are an input, every candidate is one float64 expression rounded once,
 and the keep test asks which row comes first in a total order, so nothing depends on the grid or on the order the walk visits the rows.
@@ -349,3 +350,97 @@ def test_cli_upsamples_a_sparse_raw_cloud_and_writes_a_mesh(tmp_path):
     assert objs == ["sparse_gen.obj"]
     assert re.search(r"^sparse: upsampling \(radius 0\.2, m \d+\) 1500 -> \d+ rows, 0 seeds had no plane$", r.stdout, re.M), r.stdout
     assert "dataset total data samples: 1" in r.stdout and r.stdout.count("Over!!") == 1
+
+
+# ---- every step of the input side at once ------------------------------------------------------------------------------------------------
+ALL_STEPS = dict(outlier_k=16, outlier_std=2.0, plane_threshold=0.02, cluster_radius=0.15, cluster_min_points=64, smooth_radius=0.2,
+                 upsample_radius=0.13, upsample_points=16384)
+
+
+def all_steps_scene():
+    """(5265, 6) float32: the unit sphere of 3000 rows (spacing 0.065), the table z = -1 under it as a 45 x 45 lattice over [-1.5, 1.5]^2 (spacing
+    0.068, touching the sphere), a clump of 200 rows on a sphere of radius 0.15 two units off, and 40 strays in [-4, 4]^3; unit normals"""
+    u = np.linspace(-1.5, 1.5, 45)
+    table = np.stack([*(g.ravel() for g in np.meshgrid(u, u)), np.full(45 * 45, -1.0)], 1)
+    p, n = UR.fibonacci(200)
+    clump = np.concatenate([p.astype(np.float64) * 0.15 + np.array([3.0, 0.0, 0.5]), n], 1)
+    strays = np.random.default_rng(12).uniform(-4.0, 4.0, (40, 3))
+    up = [[0.0, 0.0, 1.0]]
+    return np.concatenate([UR.file_rows("float32", 6, 3000), np.concatenate([table, np.repeat(up, 45 * 45, 0)], 1), clump,
+                           np.concatenate([strays, np.repeat(up, 40, 0)], 1)]).astype(np.float32)
+
+
+_ALL_STEPS = """
+import contextlib
+import io
+import os
+from meshanything_amd import pc_fps, pc_normals, pc_outliers, pc_plane
+from meshanything_amd.data import Dataset
+tmp = os.path.dirname(os.path.abspath(__file__))
+K = T.ALL_STEPS
+np.save(os.path.join(tmp, "scene6.npy"), T.all_steps_scene())
+np.save(os.path.join(tmp, "scene3.npy"), T.all_steps_scene()[:, :3])
+
+
+def by_hand(kind, path, uid, sampling):
+    floor = pc_upsample.MIN_ROWS                                    # upsampling is on
+    rows = np.load(path)
+    rows = pc_outliers.filter_rows(rows, K["outlier_k"], K["outlier_std"], floor, uid)
+    rows = rows[pc_plane.remove_planes(rows, K["plane_threshold"], 1024, 1, 0.2, floor, uid)]
+    rows = rows[pc_cluster.split_rows(rows, K["cluster_radius"], K["cluster_min_points"], "largest", uid)[0]]
+    rows = pc_smooth.smooth_rows(rows, K["smooth_radius"], 1, uid)
+    rows = pc_upsample.upsample_rows(rows, K["upsample_radius"], K["upsample_points"], uid)
+    if kind == "pc_xyz":
+        return pc_normals.xyz_to_pc_normal(rows, T.N_POINTS, 16, sampling=sampling)
+    if sampling == "fps":
+        return rows[pc_fps.fps_rows(rows, T.N_POINTS)]
+    return rows[np.random.choice(rows.shape[0], T.N_POINTS, replace=False)]
+
+
+for kind, uid in (("pc_normal", "scene6"), ("pc_xyz", "scene3")):
+    for sampling in ("random", "fps"):
+        tag = kind + "_" + sampling + "_"
+        path = os.path.join(tmp, uid + ".npy")
+        np.random.seed(7)
+        with contextlib.redirect_stdout(io.StringIO()) as lines:
+            ds = Dataset(kind, [path], point_sampling=sampling, **K)
+        out[tag + "dataset"], out[tag + "dataset_stdout"], out[tag + "keys"] = ds.data[0]["pc_normal"], np.array(lines.getvalue()), np.array(sorted(ds.data[0]))
+        out[tag + "len"], out[tag + "dataset_rng"] = np.array(len(ds)), np.random.get_state()[1]
+        np.random.seed(7)
+        with contextlib.redirect_stdout(io.StringIO()) as lines:
+            out[tag + "hand"] = by_hand(kind, path, uid, sampling)
+        out[tag + "hand_stdout"], out[tag + "hand_rng"] = np.array(lines.getvalue()), np.random.get_state()[1]
+"""
+
+
+@pytest.fixture(scope="module")
+def all_steps_out(tmp_path_factory):
+    return _gpu(tmp_path_factory.mktemp("pc_all_steps"), _ALL_STEPS)[0]
+
+
+@pytest.mark.parametrize("sampling", ["random", "fps"])
+@pytest.mark.parametrize("kind", ["pc_normal", "pc_xyz"])
+def test_dataset_with_every_step_on_is_the_public_functions_composed_in_order(all_steps_out, kind, sampling):
+    """outliers, plane, cluster, smooth, upsample, pick: the arrays bit for bit, the printed lines one for one and in order, the same draws
+    from the numpy RNG; and on this scene every step does something, so that no other order would give these lines"""
+    out, tag = all_steps_out, f"{kind}_{sampling}_"
+    got, want = out[tag + "dataset"], out[tag + "hand"]
+    assert int(out[tag + "len"]) == 1 and out[tag + "keys"].tolist() == ["pc_normal", "uid"]
+    assert got.shape == want.shape == (N_POINTS, 6) and got.dtype == want.dtype == np.float32 and got.tobytes() == want.tobytes()
+    lines = str(out[tag + "hand_stdout"]).splitlines()
+    assert str(out[tag + "dataset_stdout"]).splitlines() == lines + ["dataset total data samples: 1"]
+    assert np.array_equal(out[tag + "dataset_rng"], out[tag + "hand_rng"])
+    uid = "scene6" if kind == "pc_normal" else "scene3"
+    assert len(lines) == 5, lines
+    m = re.fullmatch(rf"{uid}: outlier filter removed (\d+) of 5265 points \(k = 16, threshold \S+\)", lines[0])
+    assert m and 0 < int(m.group(1)) <= 40, lines[0]
+    left = 5265 - int(m.group(1))
+    m = re.fullmatch(rf"{uid}: plane removal \(threshold 0\.02\) removed 1 plane: (\d+) inliers, normal \(\S+ \S+ \S+\), dropped (\d+) of {left} points", lines[1])
+    assert m and int(m.group(1)) == int(m.group(2)) >= 45 * 45, lines[1]
+    left -= int(m.group(2))
+    m = re.fullmatch(rf"{uid}: clustering \(radius 0\.15\) found (\d+) components, kept 1 \(sizes (\d+)\), dropped (\d+) of {left} points", lines[2])
+    assert m and int(m.group(1)) > 1 and int(m.group(3)) >= 200 and int(m.group(2)) == left - int(m.group(3)), lines[2]
+    left = int(m.group(2))
+    assert re.fullmatch(rf"{uid}: smoothing \(radius 0\.2, 1 pass\) left \d+ of {left} rows in place .*", lines[3]), lines[3]
+    m = re.fullmatch(rf"{uid}: upsampling \(radius 0\.13, m \d+\) {left} -> (\d+) rows, \d+ seeds had no plane", lines[4])
+    assert m and int(m.group(1)) >= 16384 > left, lines[4]

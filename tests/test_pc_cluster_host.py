@@ -17,7 +17,7 @@ REPO = CR.REPO
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from meshanything_amd import _lib, build, dp, mesh_export, pc_cluster, pc_outliers   # noqa: E402
+from meshanything_amd import _lib, build, dp, mesh_export, pc_cluster, pc_common, pc_outliers   # noqa: E402
 from meshanything_amd.data import Dataset, normalize_pc, pc_frame                      # noqa: E402
 
 
@@ -130,7 +130,7 @@ def test_choose_cluster_grid():
             again = pc_cluster.choose_cluster_grid(xyz.copy(), radius)
             assert origin.dtype == np.float32 and origin.shape == (3,) and dims.dtype == np.int32 and dims.shape == (3,) and isinstance(cell, np.float32)
             assert origin.tobytes() == again[0].tobytes() and cell == again[1] and dims.tobytes() == again[2].tobytes()
-            pc_outliers._check_grid((origin, cell, dims))            # within the limits always
+            pc_common.check_grid((origin, cell, dims))            # within the limits always
             assert float(cell) >= radius, (radius, cell)             # 128 cells an axis always allow it (docstring)
     origin, cell, dims = pc_cluster.choose_cluster_grid(scene, 0.06)
     assert 0.06 <= float(cell) < 0.07 and int(dims.max()) >= 30     # as fine as cell >= radius allows

@@ -16,7 +16,7 @@ REPO = R.REPO
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from meshanything_amd import _lib, build, pc_outliers             # noqa: E402
+from meshanything_amd import _lib, build, pc_common, pc_outliers             # noqa: E402
 from meshanything_amd.data import Dataset                          # noqa: E402
 
 
@@ -111,7 +111,7 @@ def test_choose_grid_is_deterministic_and_within_the_limits():
         assert _same(origin, again[0]) and cell == again[1] and _same(dims, again[2])
         assert np.isfinite(origin).all() and np.isfinite(cell) and cell > 0
         assert (dims >= 1).all() and (dims <= 128).all() and int(np.prod(dims.astype(np.int64))) <= 1 << 21
-        pc_outliers._check_grid((origin, cell, dims))
+        pc_common.check_grid((origin, cell, dims))
     origin, cell, dims = pc_outliers.choose_grid(clouds[0], 16)
     assert abs(int(dims.max()) - round(np.sqrt(12120 / 256))) <= 1 and abs(float(cell) * (round(np.sqrt(12120 / 256)) - 2) - 2.0) < 0.1   # fitted to the sphere, not to [-2, 2]^3
     assert abs(pc_outliers.choose_grid(clouds[4], 16)[2].tolist()[0] - round(np.sqrt(200000 / 256))) <= 1
