@@ -767,6 +767,42 @@ MA_API int    ma_op_pc_plane_apply(const float *ref, int N, int ref_ld, const fl
                                    int32_t *count /* or NULL */, double *moments /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_plane_workspace_bytes(int N, int H);
 
+/* ---- Voxel thinning: one surviving row per occupied voxel of a uniform grid, for --voxel_size (csrc/pc_voxel.hpp).
+ * Has no reference counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.
+ * The only cloud op that takes more than 2^22 rows: the cloud passes through in chunks and never has to be on the device at once.
+ *
+ * The rule (pcl::UniformSampling's: a surviving ROW, not VoxelGrid's centroid).  ref (n, ref_ld) fp32, xyz in the first three columns,
+ *   ref_ld = 3 or 6; origin[3] (HOST) and leaf fp32; the caller passes the per-axis minimum of the fp32 cloud as origin.  Per axis, with
+ *   no FMA contraction and the IEEE division:
+ *       t = fl32(fl32(x - o) / leaf),  i = floor(t)
+ *   A row is SKIPPED, tested in this order: a coordinate is not finite; some t is not >= 0; some i >= 2^21, which also raises the
+ *   out-of-range flag.  The voxel's key is ix << 42 | iy << 21 | iz.  The row's offset from the voxel's centre in voxel units is
+ *   e = fl32(t - ((float)i + 0.5f)), exact for i < 2^21, and d = fl32(fl32(ex*ex + ey*ey) + ez*ez).  The SURVIVOR of a voxel is its row
+ *   with the least (d, row index): a total order, so the survivor is unique and a function of the inputs alone, whatever the capacity,
+ *   the chunking and the order in which the device evaluates; a numpy float32 restatement gives the same mask byte for byte.
+ *
+ * The table: `capacity` slots, a power of two in 2 .. 2 * MA_PC_VOXEL_MAX_VOXELS, open addressing with linear probing over the 64-bit
+ *   keys, and per slot the least (bits of d) << 32 | row index; then a state block.  ma_pc_voxel_table_bytes(capacity) bytes of device
+ *   memory (0 for a capacity outside the limits).  The table may be at most HALF full: a claim that takes `used` above capacity / 2
+ *   raises the overflow flag.  Every probe loop is bounded by `capacity` steps and ends early on that flag, so a full table ends in the
+ *   flag, never in a spin.
+ *
+ * ma_op_pc_voxel_reset: every slot empty, the state zero.  Asynchronous on `stream`.
+ * ma_op_pc_voxel_insert: the rows row0 .. row0 + n - 1 of the cloud, 1 <= n <= MA_PC_VOXEL_MAX_CHUNK, row0 >= 0, row0 + n <=
+ *   MA_PC_VOXEL_MAX_POINTS; call it once per chunk with the same origin, leaf and table.  Asynchronous on `stream`.
+ * ma_op_pc_voxel_mark: keep (N) uint8 on the device: 1 for the survivor of every occupied slot, 0 elsewhere (a row index outside [0, N)
+ *   is never written); state_out (4) uint32 on the HOST: used (slots claimed), overflow, out_of_range, voxels (occupied slots counted
+ *   by this call).  It waits for `stream`, so state_out is valid on return.  With overflow or out_of_range set the mask is not a
+ *   result.  1 <= N <= MA_PC_VOXEL_MAX_POINTS. */
+#define MA_PC_VOXEL_MAX_POINTS (1 << 28)   /* a guard value: the row index fits 32 bits, the mask is 256 MB */
+#define MA_PC_VOXEL_MAX_CHUNK  (1 << 22)
+#define MA_PC_VOXEL_MAX_VOXELS (1 << 22)   /* the largest table: 2^23 slots, 128 MB */
+MA_API size_t ma_pc_voxel_table_bytes(uint64_t capacity);
+MA_API int    ma_op_pc_voxel_reset(void *table, uint64_t capacity, void *stream);
+MA_API int    ma_op_pc_voxel_insert(const float *ref, int n, int ref_ld, int64_t row0, const float *origin /* host, 3 */, float leaf, void *table,
+                                    uint64_t capacity, void *stream);
+MA_API int    ma_op_pc_voxel_mark(void *table, uint64_t capacity, uint8_t *keep, int64_t N, uint32_t *state_out /* host, 4 */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,14 @@ not have: `--sampling --num_candidates N` draws N meshes per input in one batch 
 (`meshanything_amd/mesh_score.py`); `--normal_weight W` adds W * (1 - normal consistency between the candidate's faces and the cloud's
 normals) to that ranking, and `--orient cloud` winds every written face the way the nearest cloud normals face instead of by
 `fix_normals`' signed volume (`--orient volume`, the default and the reference's behaviour).  And one input type it does not have: `--input_type pc_xyz` takes points WITHOUT normals (.npy of
-shape (N, >= 3), .xyz or .txt) and estimates them on the GPU from `--normal_k` neighbours (`meshanything_amd/pc_normals.py`).
+shape (N, >= 3), .xyz, .txt or .ply) and estimates them on the GPU from `--normal_k` neighbours (`meshanything_amd/pc_normals.py`).
+Both cloud types read `.ply` point files as scanners and photogrammetry write them (ascii, binary little or big endian): the vertex
+element's `x y z` for pc_xyz, `x y z nx ny nz` for pc_normal, float or double; faces are ignored.
+`--voxel_size L` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input file) thins a DENSE input before anything else:
+of the points in one cube of edge L, counted from the cloud's minimum corner, the one nearest the cube's centre is kept, on the GPU through
+a hash table over the cubes (`meshanything_amd/pc_voxel.py`).  It is the only step that takes more than 4194304 points, up to 268435456,
+fed through the GPU in pieces; at most 4194304 cubes may be occupied, else choose a larger L.  The later steps then cost less and see an
+even density; strays survive it one per cube, so their share rises: follow it with `--outlier_k`.  One line per input reports the rows kept.
 `--point_sampling fps` (with pc_normal and pc_xyz) keeps the 4096 points farthest-point sampling picks on the GPU
 (`meshanything_amd/pc_fps.py`) instead of the reference's uniform draw; such an input consumes no draws from the numpy RNG, so the RNG
 state later stages see differs from a `--point_sampling random` run.
@@ -74,6 +81,7 @@ STEP_FLAGS = (
     ("plane_threshold", {"plane_iters": (1024, lambda v: 1 <= v <= 65536, "in 1..65536"), "plane_count": (1, lambda v: 1 <= v <= 8, "in 1..8"),
                          "plane_min_fraction": (0.2, lambda v: 0.0 < v <= 1.0, "in (0, 1]")}),
     ("cluster_radius", {"cluster_mode": ("largest", None, None), "cluster_min_points": (4096, None, None)}),   # its two floors: after the table
+    ("voxel_size", {}),
 )
 
 
@@ -140,6 +148,10 @@ def get_args(argv=None):
                         "out: choose about one to two point spacings, and use --point_sampling fps, which thins the uneven density evenly")
     p.add_argument("--upsample_points", default=None, type=int,
                    help="with --upsample_radius: upsample an input of fewer points to at least this many (4096..4194304, default 16384 = 4 x 4096)")
+    p.add_argument("--voxel_size", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: thin a dense input first, on the GPU: keep one point per cube of this edge, in the units of "
+                        "the input file, the one nearest the cube's centre (0 = off).  The only step that takes more than 4194304 points (up to "
+                        "268435456); at most 4194304 cubes may be occupied")
     args = p.parse_args(argv)
     for switch, others in STEP_FLAGS:
         flags = [f"--{name}" for name in (switch, *others)]
@@ -147,7 +159,7 @@ def get_args(argv=None):
         if not (0.0 <= getattr(args, switch) < float("inf")):
             p.error(f"{flags[0]} must be finite and >= 0 (0 = off)")
         if args.input_type == "mesh" and (getattr(args, switch) != 0 or any(given)):
-            p.error(f"{_listed(flags)} apply to --input_type pc_normal and pc_xyz, not to mesh inputs")
+            p.error(f"{_listed(flags)} appl{'y' if others else 'ies'} to --input_type pc_normal and pc_xyz, not to mesh inputs")
         if getattr(args, switch) == 0 and any(given):
             p.error(f"{_listed(flags[1:])} need{'s' if len(others) == 1 else ''} {flags[0]} > 0")
         for name, (default, ok, wording) in others.items():
@@ -205,9 +217,9 @@ def main():
     if args.input_dir is not None:
         input_list = sorted(os.listdir(args.input_dir))
         if args.input_type == "pc_normal":
-            input_list = [os.path.join(args.input_dir, x) for x in input_list if x.endswith(".npy")]
+            input_list = [os.path.join(args.input_dir, x) for x in input_list if x.endswith(".npy") or x.lower().endswith(".ply")]
         elif args.input_type == "pc_xyz":
-            input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".npy", ".xyz", ".txt"))]
+            input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".npy", ".xyz", ".txt", ".ply"))]
         else:                                    # main.py:125-128 keeps .ply / .obj / .npy for meshes; .npy is not a mesh file, .off / .stl are read too
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".ply", ".obj", ".off", ".stl"))]
     elif args.input_path is not None:

@@ -1,9 +1,13 @@
-"""What happens to the rows of a pc_normal or pc_xyz file between loading and the pick of the rows the encoder takes: five optional steps on
+"""What happens to the rows of a pc_normal or pc_xyz file between loading and the pick of the rows the encoder takes: six optional steps on
 the GPU, none of which the reference has.  `CloudPrep` holds their options, `STAGES` lists them in the order they run, and each stage's
 function states its contract.  A step is on when its switch field is non-zero.  Off: no code path, key, print, floor or draw from the numpy
 RNG changes, and its module (pc_*.py, which needs torch) is not imported.  On: the step is looked up in its module at each call; with "mesh"
 inputs it is a ValueError.  No step draws from the global numpy RNG.  A stage function takes (its module, the options, parts, n_points, device)
-and returns parts: [(the rows that stand in for the file, the item's keys besides the cloud)], one entry until clustering splits the file."""
+and returns parts: [(the rows that stand in for the file, the item's keys besides the cloud)], one entry until clustering splits the file.
+Voxel thinning comes first because it is the only step that takes more than 2^22 rows (up to 2^28): it is what lets a dense scan in at all,
+and every later step costs less on what it leaves.  The outlier statistic then sees an even density, which it assumes; strays survive
+thinning one per voxel while the surface loses most of its rows, so the strays' share of the cloud RISES and the outlier filter after it
+matters more, not less."""
 from __future__ import annotations
 
 import importlib
@@ -11,8 +15,15 @@ from dataclasses import dataclass, fields
 from typing import Callable, NamedTuple, Optional
 
 
+def voxel(m, p, parts, n_points, device):
+    """voxel_size=L: uniform voxel thinning, once per file and before anything else (pc_voxel.thin_rows, N <= 2^28, finite): of the rows in
+    one voxel of edge L (file units), counted from the cloud's per-axis minimum, the one nearest the voxel's centre survives, the lowest row
+    among equals; at most 2^22 voxels may be occupied.  The survivors keep their order and their columns.  Fewer than the floor is a ValueError."""
+    return [(m.thin_rows(rows, p.voxel_size, p.floor(n_points), keys["uid"], device=device), keys) for rows, keys in parts]
+
+
 def outliers(m, p, parts, n_points, device):
-    """outlier_k=K: statistical outlier removal before anything else (pc_outliers.remove_statistical_outliers, K neighbours, N <= 2^22, finite):
+    """outlier_k=K: statistical outlier removal, the first of the cleaning steps (pc_outliers.remove_statistical_outliers, K neighbours, N <= 2^22, finite):
     the rows whose mean distance to their K nearest neighbours exceeds the cloud's mean by more than outlier_std standard deviations are
     dropped; the survivors keep their order.  Fewer survivors than the floor is a ValueError."""
     return [(m.filter_rows(rows, p.outlier_k, p.outlier_std, p.floor(n_points), keys["uid"], device=device), keys) for rows, keys in parts]
@@ -87,6 +98,7 @@ class Stage(NamedTuple):
 
 
 STAGES = (                                                       # in the order they run; every stage sees what the one before it left
+    Stage("voxel_size", "pc_voxel", lambda m, p, n: m.check_voxel_args(p.voxel_size), voxel),
     Stage("outlier_k", "pc_outliers", lambda m, p, n: m.check_filter_args(p.outlier_k, p.outlier_std), outliers),
     Stage("plane_threshold", "pc_plane", lambda m, p, n: m.check_remove_args(p.plane_threshold, p.plane_iters, p.plane_count, p.plane_min_fraction), plane),
     Stage("cluster_radius", "pc_cluster", check_cluster, cluster),
@@ -116,6 +128,7 @@ class CloudPrep:
     smooth_iters: int = 1
     upsample_radius: float = 0.0
     upsample_points: Optional[int] = None
+    voxel_size: float = 0.0
 
     @classmethod
     def from_args(cls, args) -> "CloudPrep":

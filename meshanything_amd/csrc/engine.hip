@@ -49,6 +49,7 @@
 #include "pc_smooth.hpp"
 #include "pc_upsample.hpp"
 #include "pc_plane.hpp"
+#include "pc_voxel.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1311,6 +1312,49 @@ int ma_op_pc_plane_apply(const float* ref, int N, int ref_ld, const float* plane
         volatile float t2 = threshold * threshold;
         const pcp::Plane pl{plane[0], plane[1], plane[2], plane[3], plane[4], plane[5], pcp::plane_rhs(plane[3], plane[4], plane[5], t2)};
         HIP_CHECK(pcp::launch_apply(ref, N, ref_ld, pl, mask, count, moments, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- voxel thinning: one surviving row per occupied voxel, through a hash table on the device (csrc/pc_voxel.hpp) ---------------------------
+static bool pc_voxel_capacity_ok(uint64_t capacity) {
+    return capacity >= 2 && capacity <= 2 * (uint64_t)MA_PC_VOXEL_MAX_VOXELS && (capacity & (capacity - 1)) == 0;
+}
+
+size_t ma_pc_voxel_table_bytes(uint64_t capacity) { return pc_voxel_capacity_ok(capacity) ? pcv::table_bytes(capacity) : 0; }
+
+int ma_op_pc_voxel_reset(void* table, uint64_t capacity, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!table) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_reset: null pointer");
+        if (!pc_voxel_capacity_ok(capacity)) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_reset: capacity must be a power of two in 2..2^23");
+        HIP_CHECK(pcv::launch_reset(table, capacity, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_voxel_insert(const float* ref, int n, int ref_ld, int64_t row0, const float* origin, float leaf, void* table, uint64_t capacity, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !origin || !table) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: null pointer");
+        if (n < 1 || n > MA_PC_VOXEL_MAX_CHUNK) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: need 1 <= n <= 2^22 rows in one call");
+        if (row0 < 0 || row0 > (int64_t)MA_PC_VOXEL_MAX_POINTS - n)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: need row0 >= 0 and row0 + n <= 2^28 rows in all");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: ref_ld must be 3 or 6");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: origin must be finite");
+        if (!std::isfinite(leaf) || !(leaf > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: leaf must be finite and > 0");
+        if (!pc_voxel_capacity_ok(capacity)) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_insert: capacity must be a power of two in 2..2^23");
+        const pcv::Grid g{origin[0], origin[1], origin[2], leaf};
+        HIP_CHECK(pcv::launch_insert(ref, n, ref_ld, (uint64_t)row0, g, table, capacity, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_voxel_mark(void* table, uint64_t capacity, uint8_t* keep, int64_t N, uint32_t* state_out, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!table || !keep || !state_out) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_mark: null pointer");
+        if (!pc_voxel_capacity_ok(capacity)) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_mark: capacity must be a power of two in 2..2^23");
+        if (N < 1 || N > (int64_t)MA_PC_VOXEL_MAX_POINTS) throw MaError(MA_ERR_INVALID, "ma_op_pc_voxel_mark: need 1 <= N <= 2^28 rows");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        HIP_CHECK(pcv::launch_mark(table, capacity, keep, (uint64_t)N, s));
+        HIP_CHECK(hipMemcpyAsync(state_out, pcv::state_of(table, capacity), pcv::STATE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
     });
 }
 

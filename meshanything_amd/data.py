@@ -42,25 +42,28 @@ class Dataset:
     mesh inputs on that GPU (mesh_input.mesh_to_pc_normal(..., device=...)): the same draws, the same clouds.
 
     `Dataset('pc_xyz', paths, normal_k=16)` has no reference counterpart: points without normals, from .npy files of shape (N, >= 3)
-    (only the first three columns are read, so the normals of an (N, 6) file are ignored) or .xyz / .txt files (np.loadtxt), N >=
-    n_points.  The same n_points rows as the pc_normal branch would draw are kept and their normals estimated from normal_k
+    (only the first three columns are read, so the normals of an (N, 6) file are ignored), .xyz / .txt files (np.loadtxt) or .ply files
+    (the vertex element's x y z; with 'pc_normal' a .ply's x y z nx ny nz are read too: mesh_input.load_ply_points), N >= n_points.
+    The same n_points rows as the pc_normal branch would draw are kept and their normals estimated from normal_k
     neighbours on the GPU (pc_normals.xyz_to_pc_normal).  It is not called 'pc': that is the reference's command-line default, a type
     its Dataset does not know and which therefore yields an empty dataset; that behaviour is restated here and pinned by the tests,
     so the new type needs a name of its own.
 
-    Every other keyword is a field of `cloud_prep.CloudPrep`, which states what it does: point_sampling, and the five optional steps
-    a pc_normal or pc_xyz file's rows go through, in the order of `cloud_prep.STAGES`, before the n_points rows are picked."""
+    Every other keyword is a field of `cloud_prep.CloudPrep`, which states what it does: point_sampling, and the six optional steps
+    a pc_normal or pc_xyz file's rows go through, in the order of `cloud_prep.STAGES`, before the n_points rows are picked.  voxel_size
+    (voxel thinning, pc_voxel.py) is the first of them: it is the only step that takes more than 2^22 rows, and with it a pc_xyz file may
+    hold up to 2^28; the outlier filter after it then sees an even density, in which the strays, kept one per voxel, have a larger share."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
                  cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
                  plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1,
-                 upsample_radius: float = 0.0, upsample_points=None):
+                 upsample_radius: float = 0.0, upsample_points=None, voxel_size: float = 0.0):
         self.data: List[Dict] = []
         prep = CloudPrep(normal_k=normal_k, point_sampling=point_sampling, outlier_k=outlier_k, outlier_std=outlier_std, plane_threshold=plane_threshold,
                          plane_iters=plane_iters, plane_count=plane_count, plane_min_fraction=plane_min_fraction, cluster_radius=cluster_radius,
                          cluster_mode=cluster_mode, cluster_min_points=cluster_min_points, smooth_radius=smooth_radius, smooth_iters=smooth_iters,
-                         upsample_radius=upsample_radius, upsample_points=upsample_points)
+                         upsample_radius=upsample_radius, upsample_points=upsample_points, voxel_size=voxel_size)
         floor = prep.check(input_type, n_points)                     # the fewest rows a file may have; every refusal that needs no file
         device = sample_device or "cuda"
 
@@ -73,15 +76,28 @@ class Dataset:
                 idx = np.random.choice(cur_data.shape[0], n_points, replace=False)
             return cur_data[idx]
 
+        def load_pc_normal(input_path):
+            if input_path.lower().endswith(".ply"):                  # a scan as it comes: x y z nx ny nz of the vertex element
+                from .mesh_input import load_ply_points
+                return load_ply_points(input_path, normals=True)
+            return np.load(input_path)
+
         def load_pc_xyz(input_path):
             from . import pc_normals
-            cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
+            if input_path.lower().endswith(".ply"):
+                from .mesh_input import load_ply_points
+                cur_data = load_ply_points(input_path)
+            else:
+                cur_data = np.load(input_path) if input_path.lower().endswith(".npy") else np.loadtxt(input_path, ndmin=2)
+            if voxel_size:                                           # thinning takes what no other step does: up to 2^28 rows
+                from . import pc_voxel
+                return pc_normals.check_xyz(cur_data, floor, normal_k, max_points=pc_voxel.MAX_POINTS)
             return pc_normals.check_xyz(cur_data, floor, normal_k)   # shape, length, finite: before anything touches the GPU
 
         def pick_pc_xyz(cur_data):
             from . import pc_normals
             return pc_normals.xyz_to_pc_normal(cur_data, n_points, normal_k, device=device, sampling=point_sampling)
-        clouds = {"pc_normal": (np.load, pick_pc_normal), "pc_xyz": (load_pc_xyz, pick_pc_xyz)}   # how a file is loaded, how its n_points rows are picked
+        clouds = {"pc_normal": (load_pc_normal, pick_pc_normal), "pc_xyz": (load_pc_xyz, pick_pc_xyz)}   # how a file is loaded, how its n_points rows are picked
         if input_type in clouds:
             load, pick = clouds[input_type]
             for input_path in input_list:

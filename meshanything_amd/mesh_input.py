@@ -87,9 +87,9 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _load_ply(path: str) -> Mesh:
-    with open(path, "rb") as f:
-        raw = f.read()
+def _ply_header(raw: bytes, path: str):
+    """The header of a PLY file's bytes -> (format, [(element, count, [("scalar", type, name) | ("list", count type, item type, name)])],
+    the offset of the body).  Shared by the mesh reader and the point reader."""
     end = raw.find(b"end_header")
     if not raw.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
@@ -111,6 +111,50 @@ def _load_ply(path: str) -> Mesh:
                 elements[-1][2].append(("scalar", _PLY_TYPES[t[1]], t[2]))
     if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
+    return fmt, elements, body
+
+
+def load_ply_points(path: str, normals: bool = False) -> np.ndarray:
+    """The vertex element of a PLY file (ascii, binary little or big endian) as a point cloud: (N, 3) x y z, with normals (N, 6) x y z nx ny
+    nz; float32 if the file declares all of them float, else float64.  Faces and any other element or property are ignored.  The table is
+    read through numpy in one piece (a scan has 10^7 rows).  A missing property is a ValueError that names it."""
+    import io
+    with open(path, "rb") as f:
+        raw = f.read()
+    fmt, elements, body = _ply_header(raw, path)
+    want = ["x", "y", "z"] + (["nx", "ny", "nz"] if normals else [])
+    at = next((j for j, e in enumerate(elements) if e[0] == "vertex"), None)
+    if at is None:
+        raise ValueError(f"{path}: the PLY file has no vertex element")
+    _, count, props = elements[at]
+    if any(p[0] != "scalar" for e in elements[:at + 1] for p in e[2]):
+        raise ValueError(f"{path}: a list property in or before the vertex element is not supported for point clouds")
+    names = [p[2] for p in props]
+    for name in want:
+        if name not in names:
+            raise ValueError(f"{path}: the vertex element has no property {name!r}" + (" (--input_type pc_normal needs nx ny nz)" if name.startswith("n") else ""))
+    types = {p[2]: p[1] for p in props}
+    if any(types[name] not in ("f4", "f8") for name in want):
+        raise ValueError(f"{path}: the vertex properties {' '.join(want)} must be float or double")
+    out = np.float32 if all(types[name] == "f4" for name in want) else np.float64
+    if fmt == "ascii":
+        table = np.loadtxt(io.BytesIO(raw[body:]), skiprows=sum(e[1] for e in elements[:at]), max_rows=count, ndmin=2, dtype=np.float64) if count else np.zeros((0, len(names)))
+        if table.shape != (count, len(names)):
+            raise ValueError(f"{path}: the vertex element should hold {count} rows of {len(names)} values, found {table.shape}")
+        return np.ascontiguousarray(table[:, [names.index(name) for name in want]], dtype=out)
+    bo = "<" if fmt == "binary_little_endian" else ">"
+    pos = body + sum(np.dtype([(p[2], bo + p[1]) for p in e[2]]).itemsize * e[1] for e in elements[:at] if e[2])
+    dt = np.dtype([(p[2], bo + p[1]) for p in props])
+    if pos + dt.itemsize * count > len(raw):
+        raise ValueError(f"{path}: the file ends before its {count} vertices do")
+    arr = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
+    return np.stack([arr[name].astype(out) for name in want], axis=1)
+
+
+def _load_ply(path: str) -> Mesh:
+    with open(path, "rb") as f:
+        raw = f.read()
+    fmt, elements, body = _ply_header(raw, path)
     verts = np.zeros((0, 3))
     polys: List[List[int]] = []
     if fmt == "ascii":

@@ -135,15 +135,18 @@ def orient_normals(points, normals, nbr_idx) -> np.ndarray:
     return n
 
 
-def check_xyz(xyz, n_points: int, k: int) -> np.ndarray:
-    """The checks of xyz_to_pc_normal that need no device; returns xyz as an array."""
+def check_xyz(xyz, n_points: int, k: int, max_points=None) -> np.ndarray:
+    """The checks of xyz_to_pc_normal that need no device; returns xyz as an array.  max_points: the row cap of a file that voxel thinning
+    (pc_voxel.py) reduces before anything else sees it, instead of 2^22."""
     xyz = as_host_cloud(xyz)
     k = check_k(k)
     if n_points < k:
         raise ValueError(f"n_points = {n_points} is less than k = {k}")
     if xyz.shape[0] < n_points:
         raise ValueError(f"a pc_xyz input should have at least {n_points} points, got {xyz.shape[0]}")
-    if xyz.shape[0] > MAX_POINTS:
+    if max_points is not None and xyz.shape[0] > max_points:
+        raise ValueError(f"a pc_xyz input may have at most {max_points} points with voxel thinning, got {xyz.shape[0]}")
+    if max_points is None and xyz.shape[0] > MAX_POINTS:
         raise ValueError(f"a pc_xyz input may have at most 2^22 points, got {xyz.shape[0]}")
     if n_points > MAX_QUERIES:
         raise ValueError(f"n_points may be at most 2^20, got {n_points}")
