@@ -803,6 +803,34 @@ MA_API int    ma_op_pc_voxel_insert(const float *ref, int n, int ref_ld, int64_t
                                     uint64_t capacity, void *stream);
 MA_API int    ma_op_pc_voxel_mark(void *table, uint64_t capacity, uint8_t *keep, int64_t N, uint32_t *state_out /* host, 4 */, void *stream);
 
+/* ---- The tightest box: the extents of a cloud under candidate rotations, for --align_iters (csrc/pc_align.hpp).
+ * Has no reference counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.
+ * Device arrays (`centre` is a HOST array of three floats), caller-owned workspace, asynchronous on `stream`.
+ *
+ * ma_op_pc_align_extents: ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6; rot (H, 9) fp32, hypothesis h as a
+ *   row-major 3x3 r, which need not be orthonormal (the caller's concern).  The rule, with no FMA contraction, for row p and axis a:
+ *       q   = fl32(p - centre) per axis
+ *       u_a = fl32(fl32(fl32(r_a0*qx) + fl32(r_a1*qy)) + fl32(r_a2*qz)) + 0.0f
+ *   The + 0.0f turns -0 into +0, so min and max never depend on the order in which a -0 and a +0 meet.  lo_a = the min of u_a over the
+ *   rows, hi_a the max.  A hypothesis is BAD iff one of its nine entries, or one u_a of one row, is not finite.
+ *   Each output may be NULL, at least one must be given:
+ *   extents (H, 6) fp32 = lo0, lo1, lo2, hi0, hi1, hi2; six NaN for a bad hypothesis.
+ *   volumes (H) float64 = ((double)hi0 - (double)lo0) * ((double)hi1 - (double)lo1), then * ((double)hi2 - (double)lo2), each operation
+ *   rounded once; +inf for a bad hypothesis (every other volume is finite).
+ *   best (1) int32 = the hypothesis of the least volume among those not bad, the lowest index among equals, -1 if every one is bad.
+ *   Min and max are order-independent and the workgroups combine through integer atomics on a monotone key of the float's bits (no
+ *   floating-point atomics): the outputs are a function of the inputs alone, EQUAL to a numpy float32 restatement's and identical on a
+ *   second run.  1 <= N <= MA_PC_ALIGN_MAX_POINTS, 1 <= H <= MA_PC_ALIGN_MAX_HYPOTHESES.
+ *
+ * workspace: ma_pc_align_workspace_bytes(N, H) bytes of device memory (0 for arguments outside the limits): eight words and one float64
+ *   per hypothesis; its contents on entry do not matter. */
+#define MA_PC_ALIGN_MAX_POINTS      (1 << 22)
+#define MA_PC_ALIGN_MAX_HYPOTHESES  (1 << 16)
+MA_API int    ma_op_pc_align_extents(const float *ref, int N, int ref_ld, const float *centre /* host, 3 */, const float *rot, int H,
+                                     float *extents /* or NULL */, double *volumes /* or NULL */, int32_t *best /* or NULL */,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_align_workspace_bytes(int N, int H);
+
 #ifdef __cplusplus
 }
 #endif

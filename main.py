@@ -59,6 +59,15 @@ reports m and the rows before and after.  With it an input file, the survivors o
 to 64 points instead of 4096.  The patches are flat, an open border grows outward by up to R, and at a sharp edge the fitted plane is
 diagonal and the patch sticks out: choose R at about one to two point spacings, and use `--point_sampling fps`, since a uniform draw
 follows the uneven density that patches of different size leave.
+`--align_iters H` (with pc_normal and pc_xyz; 0 = off, the default; 256..65536) then aligns what is left to its tightest box, once per kept
+part and before sampling: the input is centred and scaled by its AXIS-ALIGNED box and the mesh lies on a 128-step lattice along the same
+axes, so a scan that sits askew in its file wastes resolution on empty corners and shows the decoder a turned shape.  H rotations from a
+private generator (the numpy RNG is not touched) are scored on the GPU by the volume of the box around the turned points
+(`meshanything_amd/pc_align.py`), over all rotations first and then `--align_rounds` times (default 4, 0..8) over ever smaller balls about
+the best so far, whose radii follow from H.  Of the 24 equivalent frames of a box the one nearest the file's is taken, so an up that is
+roughly right stays up; unless the box shrinks by more than `--align_min_gain` (default 0.02, in [0, 1)) the input keeps its axes: a
+ball has no orientation to find.  One line per part reports the angle, the axis and the box volumes.  The mesh is written in the aligned
+frame, except with `--cluster_mode split`, whose files are in the INPUT's coordinates as before.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -73,7 +82,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-# The input steps whose switch is a distance (0 = off), in the order their errors are reported: the switch, then the flags that need it as
+# The input steps whose switch is a distance or, for --align_iters, a count (0 = off), in the order their errors are reported: the switch, then the flags that need it as
 # {flag: (default, range test or None, the range's wording)}.  The fifth step's --outlier_k and --outlier_std follow another pattern, below.
 STEP_FLAGS = (
     ("upsample_radius", {"upsample_points": (4 * 4096, lambda v: 4096 <= v <= 1 << 22, "in 4096..4194304")}),
@@ -82,6 +91,7 @@ STEP_FLAGS = (
                          "plane_min_fraction": (0.2, lambda v: 0.0 < v <= 1.0, "in (0, 1]")}),
     ("cluster_radius", {"cluster_mode": ("largest", None, None), "cluster_min_points": (4096, None, None)}),   # its two floors: after the table
     ("voxel_size", {}),
+    ("align_iters", {"align_rounds": (4, lambda v: 0 <= v <= 8, "in 0..8"), "align_min_gain": (0.02, lambda v: 0.0 <= v < 1.0, "in [0, 1)")}),
 )
 
 
@@ -152,6 +162,13 @@ def get_args(argv=None):
                    help="with --input_type pc_normal / pc_xyz: thin a dense input first, on the GPU: keep one point per cube of this edge, in the units of "
                         "the input file, the one nearest the cube's centre (0 = off).  The only step that takes more than 4194304 points (up to "
                         "268435456); at most 4194304 cubes may be occupied")
+    p.add_argument("--align_iters", default=0, type=int,
+                   help="with --input_type pc_normal / pc_xyz: turn the input into the frame of its tightest box before sampling: this many rotations "
+                        "per round, scored on the GPU by the volume of the box around the turned points (256..65536; 0 = off)")
+    p.add_argument("--align_rounds", default=None, type=int,
+                   help="with --align_iters: refinement rounds after the one over all rotations, each over a smaller ball about the best so far (0..8, default 4)")
+    p.add_argument("--align_min_gain", default=None, type=float,
+                   help="with --align_iters: keep the file's axes unless the box shrinks by more than this fraction (in [0, 1), default 0.02)")
     args = p.parse_args(argv)
     for switch, others in STEP_FLAGS:
         flags = [f"--{name}" for name in (switch, *others)]
@@ -167,6 +184,8 @@ def get_args(argv=None):
                 setattr(args, name, default)
             elif ok is not None and not ok(getattr(args, name)):
                 p.error(f"--{name} must be {wording}")
+    if args.align_iters != 0 and not 256 <= args.align_iters <= 65536:
+        p.error("--align_iters must be 0 (off) or in 256..65536")
     if args.upsample_radius > 0 and args.cluster_min_points < 64:            # the default passes both
         p.error("--cluster_min_points must be at least 64, the rows upsampling takes")
     if args.upsample_radius == 0 and args.cluster_min_points < 4096:
@@ -196,9 +215,8 @@ def main():
     from meshanything_amd import dp
     from meshanything_amd.checkpoint import load_safetensors_items, synthetic_items
     from meshanything_amd.cloud_prep import CloudPrep
-    from meshanything_amd.data import Dataset, uid_of
+    from meshanything_amd.data import Dataset, to_file_frame, uid_of
     from meshanything_amd.mesh_export import faces_from_coords, fix_normals, merge_meshes, write_obj
-    from meshanything_amd.mesh_score import DEFAULT_MESH_SCALE
     from meshanything_amd.model import MeshAnything
 
     args = get_args()
@@ -264,9 +282,8 @@ def main():
             verts, faces = faces_from_coords(coords)
             if orient is None:                       # --orient cloud: the winding came with the coordinates
                 faces = fix_normals(verts, faces)
-            if split:                                # into the input file's frame, in float64: the decoder's +-0.5 times 2 is the unit box
-                centre, scale = d["frame"]
-                verts = centre[None, :] + scale * DEFAULT_MESH_SCALE * verts.astype(np.float64)
+            if split:                                # into the input file's frame, in float64, out of the aligned one if --align_iters turned the part
+                verts = to_file_frame(verts, d["frame"], d.get("pose"))
             path = os.path.join(out_dir, f'{d["uid"]}_gen.obj')
             write_obj(path, verts, faces)
             print(f"{path} Over!!")

@@ -7,7 +7,8 @@ and returns parts: [(the rows that stand in for the file, the item's keys beside
 Voxel thinning comes first because it is the only step that takes more than 2^22 rows (up to 2^28): it is what lets a dense scan in at all,
 and every later step costs less on what it leaves.  The outlier statistic then sees an even density, which it assumes; strays survive
 thinning one per voxel while the surface loses most of its rows, so the strays' share of the cloud RISES and the outlier filter after it
-matters more, not less."""
+matters more, not less.  After the six, and before the pick, comes a step of its own kind, `POSE` (align_iters): it drops and adds no row but
+turns every kept part into the frame of its tightest box, and the part's keys gain "pose", with which the turn can be undone."""
 from __future__ import annotations
 
 import importlib
@@ -82,6 +83,20 @@ def upsample(m, p, parts, n_points, device):
     return out
 
 
+def align(m, p, parts, n_points, device):
+    """align_iters=H: alignment to the tightest box, once per kept part, on what upsampling left and before the pick (pc_align.align_rows,
+    N <= 2^22, finite): 1 + align_rounds times (rounds 0..8), H rotations (256..65 536) from a private generator are scored on the GPU by the
+    volume of the part's axis-aligned box under them, all rotations first and then ever smaller balls about the best so far; if the best
+    box is smaller than the file's by more than align_min_gain (in [0, 1)), the part is turned about its bounding-box mid-point c into the
+    frame R' of that box, the one of its 24 equivalents nearest the file's, normals included, else it is left as it is.  The keys gain
+    "pose": (R', c), which `Dataset.__getitem__` passes on and `data.to_file_frame` undoes.  Not one of STAGES: no row comes or goes."""
+    out = []
+    for rows, keys in parts:
+        rows, pose = m.align_rows(rows, p.align_iters, p.align_rounds, p.align_min_gain, keys["uid"], device=device)
+        out.append((rows, {**keys, "pose": pose}))
+    return out
+
+
 def check_cluster(m, p, n_points):
     m.check_split_args(p.cluster_radius, p.cluster_min_points, p.cluster_mode)
     if p.cluster_min_points < p.floor(n_points):
@@ -104,7 +119,8 @@ STAGES = (                                                       # in the order 
     Stage("cluster_radius", "pc_cluster", check_cluster, cluster),
     Stage("smooth_radius", "pc_smooth", lambda m, p, n: m.check_smooth_args(p.smooth_radius, p.smooth_iters), smooth),
     Stage("upsample_radius", "pc_upsample", lambda m, p, n: m.check_upsample_args(p.upsample_radius, p.upsample_target(n), n), upsample),
-)                                                                # then the pick: the uniform draw, FPS, or the pc_xyz normal estimate (data.Dataset)
+)                                                                # then POSE, then the pick: the uniform draw, FPS, or the pc_xyz normal estimate (data.Dataset)
+POSE = Stage("align_iters", "pc_align", lambda m, p, n: m.check_align_args(p.align_iters, p.align_rounds, p.align_min_gain), align)
 
 
 @dataclass(frozen=True)
@@ -129,6 +145,9 @@ class CloudPrep:
     upsample_radius: float = 0.0
     upsample_points: Optional[int] = None
     voxel_size: float = 0.0
+    align_iters: int = 0
+    align_rounds: int = 4
+    align_min_gain: float = 0.02
 
     @classmethod
     def from_args(cls, args) -> "CloudPrep":
@@ -139,6 +158,10 @@ class CloudPrep:
         """The stages that are on, each with its module."""
         return [(s, importlib.import_module(f".{s.module}", __package__)) for s in STAGES if getattr(self, s.switch)]
 
+    def pose(self):
+        """[(POSE, its module)] if alignment is on, else []."""
+        return [(POSE, importlib.import_module(f".{POSE.module}", __package__))] if self.align_iters else []
+
     def floor(self, n_points: int) -> int:
         """The fewest rows a file, and what a step leaves of it, may have."""
         return min(importlib.import_module(".pc_upsample", __package__).MIN_ROWS, n_points) if self.upsample_radius else n_points
@@ -147,22 +170,22 @@ class CloudPrep:
         return 4 * n_points if self.upsample_points is None else self.upsample_points
 
     def check(self, input_type: str, n_points: int) -> int:
-        """Everything that can be refused before a file is read, upsampling's options first, then in stage order -> the floor."""
+        """Everything that can be refused before a file is read, upsampling's options first, then in stage order, then alignment's -> the floor."""
         if self.point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {self.point_sampling!r}')
         if self.point_sampling == "fps" and input_type == "mesh":
             raise ValueError('point_sampling="fps" applies to pc_normal and pc_xyz inputs: the points of a mesh input are already drawn from its surface')
         if not self.upsample_radius and self.upsample_points is not None:
             raise ValueError("upsample_points needs upsample_radius > 0")
-        for stage, module in sorted(self.on(), key=lambda sm: sm[0].switch != "upsample_radius"):
+        for stage, module in sorted(self.on(), key=lambda sm: sm[0].switch != "upsample_radius") + self.pose():
             if input_type == "mesh":
                 raise ValueError(f"{stage.switch} {stage.mesh}")
             stage.check(module, self, n_points)
         return self.floor(n_points)
 
     def parts(self, rows, uid: str, device, n_points: int = 4096):
-        """The rows of one file -> [(rows, keys)] after every stage that is on: the file itself, or its kept components."""
+        """The rows of one file -> [(rows, keys)] after every stage that is on and the alignment: the file itself, or its kept components."""
         parts = [(rows, {"uid": uid})]
-        for stage, module in self.on():
+        for stage, module in self.on() + self.pose():
             parts = stage.apply(module, self, parts, n_points, device)
         return parts

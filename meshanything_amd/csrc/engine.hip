@@ -48,6 +48,7 @@
 #include "pc_cluster.hpp"
 #include "pc_smooth.hpp"
 #include "pc_upsample.hpp"
+#include "pc_align.hpp"
 #include "pc_plane.hpp"
 #include "pc_voxel.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
@@ -1312,6 +1313,24 @@ int ma_op_pc_plane_apply(const float* ref, int N, int ref_ld, const float* plane
         volatile float t2 = threshold * threshold;
         const pcp::Plane pl{plane[0], plane[1], plane[2], plane[3], plane[4], plane[5], pcp::plane_rhs(plane[3], plane[4], plane[5], t2)};
         HIP_CHECK(pcp::launch_apply(ref, N, ref_ld, pl, mask, count, moments, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- the tightest box: extents, volumes and the best of up to 2^16 rotations (csrc/pc_align.hpp) -------------------------------------------
+static bool pc_align_shape_ok(int N, int H) { return N >= 1 && N <= MA_PC_ALIGN_MAX_POINTS && H >= 1 && H <= MA_PC_ALIGN_MAX_HYPOTHESES; }
+
+size_t ma_pc_align_workspace_bytes(int N, int H) { return pc_align_shape_ok(N, H) ? pca::layout(N, H).bytes : 0; }
+
+int ma_op_pc_align_extents(const float* ref, int N, int ref_ld, const float* centre, const float* rot, int H, float* extents, double* volumes,
+                           int32_t* best, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !centre || !rot || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_align_extents: null pointer");
+        if (!extents && !volumes && !best) throw MaError(MA_ERR_INVALID, "ma_op_pc_align_extents: at least one of extents, volumes and best must be given");
+        if (!pc_align_shape_ok(N, H)) throw MaError(MA_ERR_INVALID, "ma_op_pc_align_extents: need 1 <= N <= 2^22 and 1 <= H <= 2^16");
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_align_extents: ref_ld must be 3 or 6");
+        if (workspace_bytes < pca::layout(N, H).bytes)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_align_extents: workspace smaller than ma_pc_align_workspace_bytes(N, H)");
+        HIP_CHECK(pca::launch_extents(ref, N, ref_ld, centre, rot, H, extents, volumes, best, workspace, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

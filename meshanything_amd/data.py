@@ -31,6 +31,19 @@ def pc_frame(pc_normal: np.ndarray):
     return centre, float(np.abs(pc_coor - centre[None, :]).max() / 0.9995)
 
 
+def to_file_frame(verts: np.ndarray, frame, pose=None) -> np.ndarray:
+    """Mesh vertices in the decoder's +-0.5 box -> the input file's coordinates, in float64: the inverse of the normalisation, centre +
+    scale * 2 * v with frame = `pc_frame`'s (centre, scale) (times 2: the decoder's +-0.5 is the unit box), and then, with pose = (R', c) of
+    `pc_align.align_rows`, the inverse of the alignment, c + R'T (x - c)."""
+    from .mesh_score import DEFAULT_MESH_SCALE
+    centre, scale = frame
+    verts = centre[None, :] + scale * DEFAULT_MESH_SCALE * verts.astype(np.float64)
+    if pose is not None:
+        R, c = pose
+        verts = c[None, :] + (verts - c[None, :]) @ R                # rows times R = R'T times columns
+    return verts
+
+
 def uid_of(input_path: str) -> str:
     """main.py:27,39: the sample's name, the file name up to its first dot."""
     return input_path.split("/")[-1].split(".")[0]
@@ -52,18 +65,23 @@ class Dataset:
     Every other keyword is a field of `cloud_prep.CloudPrep`, which states what it does: point_sampling, and the six optional steps
     a pc_normal or pc_xyz file's rows go through, in the order of `cloud_prep.STAGES`, before the n_points rows are picked.  voxel_size
     (voxel thinning, pc_voxel.py) is the first of them: it is the only step that takes more than 2^22 rows, and with it a pc_xyz file may
-    hold up to 2^28; the outlier filter after it then sees an even density, in which the strays, kept one per voxel, have a larger share."""
+    hold up to 2^28; the outlier filter after it then sees an even density, in which the strays, kept one per voxel, have a larger share.
+    After the six, on what they left and before the pick, align_iters (alignment to the tightest box, pc_align.py) turns every kept part into
+    the frame in which its bounding box is smallest: `normalize_pc` and the decoder's lattice work along the axes, and a scan that sits askew
+    in its file wastes them.  Such an item carries "pose": (R', c), the turn and its fixed point."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
                  cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
                  plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1,
-                 upsample_radius: float = 0.0, upsample_points=None, voxel_size: float = 0.0):
+                 upsample_radius: float = 0.0, upsample_points=None, voxel_size: float = 0.0, align_iters: int = 0, align_rounds: int = 4,
+                 align_min_gain: float = 0.02):
         self.data: List[Dict] = []
         prep = CloudPrep(normal_k=normal_k, point_sampling=point_sampling, outlier_k=outlier_k, outlier_std=outlier_std, plane_threshold=plane_threshold,
                          plane_iters=plane_iters, plane_count=plane_count, plane_min_fraction=plane_min_fraction, cluster_radius=cluster_radius,
                          cluster_mode=cluster_mode, cluster_min_points=cluster_min_points, smooth_radius=smooth_radius, smooth_iters=smooth_iters,
-                         upsample_radius=upsample_radius, upsample_points=upsample_points, voxel_size=voxel_size)
+                         upsample_radius=upsample_radius, upsample_points=upsample_points, voxel_size=voxel_size, align_iters=align_iters,
+                         align_rounds=align_rounds, align_min_gain=align_min_gain)
         floor = prep.check(input_type, n_points)                     # the fewest rows a file may have; every refusal that needs no file
         device = sample_device or "cuda"
 
@@ -144,4 +162,6 @@ class Dataset:
         item = {"pc_normal": normalize_pc(d["pc_normal"]), "uid": d["uid"]}
         if "group" in d:
             item.update(group=d["group"], part=d["part"], frame=pc_frame(d["pc_normal"]))
+        if "pose" in d:
+            item["pose"] = d["pose"]
         return item
