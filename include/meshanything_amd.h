@@ -831,6 +831,66 @@ MA_API int    ma_op_pc_align_extents(const float *ref, int N, int ref_ld, const 
                                      void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_align_workspace_bytes(int N, int H);
 
+/* ---- Rigid registration of two clouds: one ICP iteration over the cell grid, for --register_dist (csrc/pc_register.hpp; DESIGN.md
+ * section 21); PCL's registration module and Open3D's registration_icp do the same job.  Has no reference counterpart.  Needs no engine;
+ * errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device arrays (origin, dims, pose, centre and
+ * pair_bound are HOST pointers), caller-owned workspace.
+ *
+ * ma_op_pc_register_build: target (N, target_ld) and source (M, source_ld) fp32, xyz in the first three columns, each ld = 3 or 6.  Bins
+ *   the target over the grid (origin, cell, dims: as for ma_op_pc_knn_grid, the same faces and cell rule), and bins the source ONCE, in
+ *   its own frame, so that the step's search threads take source rows in cell order; a rigid motion keeps neighbours neighbours, so one
+ *   build serves every pose.  Asynchronous on `stream`.  The grid only decides the time.
+ *
+ * ma_op_pc_register_step: the same clouds and grid, over the workspace ma_op_pc_register_build filled.  NOT asynchronous: it reads the
+ *   pair bound back on `stream` before it launches the search, as ma_op_pc_cluster does.  pose: 12 floats, R row-major, then t; centre: 3
+ *   floats; r2 = fl32(max_dist * max_dist), computed once on the host.  With no FMA contraction anywhere, for source row (x, y, z):
+ *       p'_a = fl32(fl32(fl32(fl32(R_a0 * x) + fl32(R_a1 * y)) + fl32(R_a2 * z)) + t_a)
+ *       d    = fl32(fl32(dx * dx + dy * dy) + dz * dz),  dx = fl32(p'_x - q_x), ...   against target row q: the key of ma_op_pc_knn
+ *   The PAIR of the source row is the target row least in (d, index) among the rows with d <= r2: equality is included, a NaN key pairs
+ *   nothing, of duplicate target rows the lower index wins.  nn_idx (M) int32 = that row, -1 if there is none; nn_d2 (M) fp32 = its d,
+ *   +inf if there is none; both in the source's ORIGINAL row order, a function of the clouds, the pose and max_dist alone -- not of the
+ *   grid, the workspace's earlier contents or the run -- so a numpy float32 restatement over all rows gives EQUAL arrays.
+ *   The walk is ma_op_pc_knn_grid's ring walk from the cell of p' in the target's grid; it ends at the whole grid, when the pair's key
+ *   is STRICTLY below fl32(b * b) for every side of the block that is not a grid border (that call's rule (b) with k = 1), or when
+ *   every such side has fl32(b * b) > r2 (ma_op_pc_cluster's rule).
+ *   Guard, per call: the transformed source is counted into the target's cells, and sum_c m_c * (target rows in the block of R rings
+ *   around c), R = floor(max_dist / cell) + 2, a bound on the keys the search evaluates, is written to *pair_bound (if given); above
+ *   max_pairs (0 = MA_PC_CLUSTER_MAX_PAIRS) the call fails with MA_ERR_INVALID, the message giving both numbers, launches nothing
+ *   further and writes no output.  A grid whose float32 faces would break the bound is refused before any device work.
+ *   sums (MA_PC_REGISTER_SUMS) float64 on the device, over the pairs, c = centre, every term formed in float64 from the float32 p' and q:
+ *       [0] pairs used   [1] sum (double)d   [30] pairs skipped   [31] 0
+ *     target_normals = NULL, the point metric:  [2..4] sum (p' - c)   [5..7] sum (q - c)   [8..16] sum (p' - c)(q - c)^T, row-major
+ *     target_normals (row j at target_normals + j * normals_ld, fp32, normals_ld >= 3; pass target + 3 with ld 6 for a cloud that carries
+ *     its normals), the plane metric:  n = normal / sqrt((nx*nx + ny*ny) + nz*nz), e = p' - q, r = (n_x*e_x + n_y*e_y) + n_z*e_z,
+ *       u = p' - c, a = u x n (a_x = u_y*n_z - u_z*n_y and cyclically), J = (a, n):
+ *       [2] sum r*r   [3..8] sum J_k * r   [9..29] sum J_k * J_l for k <= l, row-major.  A pair whose normal is zero or not finite is
+ *       SKIPPED: it counts in [30] and in nothing else.
+ *   The sums are formed in a FIXED order and with no floating-point atomics: thread t of workgroup g adds source rows g * 256 * RPT + j *
+ *   256 + t for j = 0 .. RPT - 1 (RPT = MA_PC_REGISTER_ROWS_PER_THREAD), then a tree over the MA_PC_REGISTER_THREADS lanes (lane t += lane
+ *   t + w, w = 128, 64, .., 1), then one workgroup adds the workgroups' partials in index order.  The same inputs give the same 32
+ *   doubles for every grid, every workspace content and every run; against another summation order they agree within depth * 2^-52 *
+ *   sum |term| per slot, depth = RPT + 8 + ceil(M / (256 * RPT)).
+ *   Each of nn_idx, nn_d2, pair_bound and sums may be NULL; at least one of nn_idx, nn_d2 and sums must be given.
+ *   Non-finite coordinates: a source row with a non-finite p' pairs nothing and adds no term; nothing is read or written out of bounds.
+ *   1 <= N, M <= MA_PC_GRID_MAX_POINTS, pose and centre finite, max_dist finite and > 0 with a finite square, the grid limits of
+ *   ma_op_pc_knn_grid, max_dist / cell <= 8.
+ *
+ * workspace: ma_pc_register_workspace_bytes(N, M, nx, ny, nz) bytes of device memory (0 for arguments outside the limits): the grid
+ *   layouts of both clouds, the 8-byte total, a count per cell, M indices and the partial sums; its contents before the build do not matter. */
+#define MA_PC_REGISTER_SUMS            32
+#define MA_PC_REGISTER_THREADS         256
+#define MA_PC_REGISTER_ROWS_PER_THREAD 16
+MA_API int    ma_op_pc_register_build(const float *target, int N, int target_ld, const float *source, int M, int source_ld,
+                                      const float *origin, float cell, const int32_t *dims, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+MA_API int    ma_op_pc_register_step(const float *target, int N, int target_ld, const float *source, int M, int source_ld,
+                                     const float *origin, float cell, const int32_t *dims, const float *pose /* host, 12 */,
+                                     const float *centre /* host, 3 */, float max_dist, const float *target_normals /* or NULL */,
+                                     int normals_ld, uint64_t max_pairs /* 0 = MA_PC_CLUSTER_MAX_PAIRS */, int32_t *nn_idx /* or NULL */,
+                                     float *nn_d2 /* or NULL */, uint64_t *pair_bound /* host pointer or NULL */, double *sums /* or NULL */,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+MA_API size_t ma_pc_register_workspace_bytes(int N, int M, int nx, int ny, int nz);
+
 #ifdef __cplusplus
 }
 #endif

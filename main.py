@@ -68,6 +68,16 @@ the best so far, whose radii follow from H.  Of the 24 equivalent frames of a bo
 roughly right stays up; unless the box shrinks by more than `--align_min_gain` (default 0.02, in [0, 1)) the input keeps its axes: a
 ball has no orientation to find.  One line per part reports the angle, the axis and the box volumes.  The mesh is written in the aligned
 frame, except with `--cluster_mode split`, whose files are in the INPUT's coordinates as before.
+`--register_dist D` (with pc_normal and pc_xyz; 0 = off, the default; in the units of the input files) takes objects that come as several
+partial scans, each in its own, roughly known, pose: a sub-directory of `--input_dir`, or a directory given as `--input_path`, is ONE object,
+its point files in sorted order are its scans and its name names the output.  The first scan is the frame; every further scan is moved
+onto the union of the ones before it by ICP on the GPU (`meshanything_amd/pc_register.py`): per iteration the nearest point within D of
+every point, over the same cell grid, and a least-squares step on the point-to-plane distances (`--register_metric point`: point-to-point,
+for clouds without usable normals; pc_xyz scans get normals from `--normal_k` neighbours within each scan), at most `--register_iters`
+times (default 30, 1..256) or until the RMS changes by at most `--register_tol` of itself (default 1e-6, in [0, 1)).  The scans must start
+within D of their place: a scan of whose points less than `--register_min_overlap` (default 0.3, in (0, 1]) find a partner is an error, not
+a guess.  With `--voxel_size` each scan is thinned before, and the union again after, where overlapping scans doubled the density.  One
+line per scan reports iterations, the paired share, the RMS and the motion.  No global (featureless) alignment, no loop closure.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -92,6 +102,8 @@ STEP_FLAGS = (
     ("cluster_radius", {"cluster_mode": ("largest", None, None), "cluster_min_points": (4096, None, None)}),   # its two floors: after the table
     ("voxel_size", {}),
     ("align_iters", {"align_rounds": (4, lambda v: 0 <= v <= 8, "in 0..8"), "align_min_gain": (0.02, lambda v: 0.0 <= v < 1.0, "in [0, 1)")}),
+    ("register_dist", {"register_iters": (30, lambda v: 1 <= v <= 256, "in 1..256"), "register_tol": (1e-6, lambda v: 0.0 <= v < 1.0, "in [0, 1)"),
+                       "register_metric": ("plane", None, None), "register_min_overlap": (0.3, lambda v: 0.0 < v <= 1.0, "in (0, 1]")}),
 )
 
 
@@ -169,6 +181,17 @@ def get_args(argv=None):
                    help="with --align_iters: refinement rounds after the one over all rotations, each over a smaller ball about the best so far (0..8, default 4)")
     p.add_argument("--align_min_gain", default=None, type=float,
                    help="with --align_iters: keep the file's axes unless the box shrinks by more than this fraction (in [0, 1), default 0.02)")
+    p.add_argument("--register_dist", default=0.0, type=float,
+                   help="with --input_type pc_normal / pc_xyz: a directory (--input_path, or a sub-directory of --input_dir) is one object and its point "
+                        "files are partial scans: register each onto the ones before it by ICP on the GPU, pairing points at most this far apart, in the "
+                        "units of the input files, and merge them (0 = off)")
+    p.add_argument("--register_iters", default=None, type=int, help="with --register_dist: ICP iterations per scan at the most (1..256, default 30)")
+    p.add_argument("--register_tol", default=None, type=float,
+                   help="with --register_dist: stop when the RMS changes by at most this fraction of itself (in [0, 1), default 1e-6)")
+    p.add_argument("--register_metric", default=None, choices=["plane", "point"],
+                   help="with --register_dist: point-to-plane distances (the default) or point-to-point, for clouds without usable normals")
+    p.add_argument("--register_min_overlap", default=None, type=float,
+                   help="with --register_dist: refuse a scan of whose points less than this fraction find a partner (in (0, 1], default 0.3)")
     args = p.parse_args(argv)
     for switch, others in STEP_FLAGS:
         flags = [f"--{name}" for name in (switch, *others)]
@@ -234,12 +257,14 @@ def main():
 
     if args.input_dir is not None:
         input_list = sorted(os.listdir(args.input_dir))
+        scans = [os.path.join(args.input_dir, x) for x in input_list if args.register_dist > 0 and os.path.isdir(os.path.join(args.input_dir, x))]
         if args.input_type == "pc_normal":
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.endswith(".npy") or x.lower().endswith(".ply")]
         elif args.input_type == "pc_xyz":
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".npy", ".xyz", ".txt", ".ply"))]
         else:                                    # main.py:125-128 keeps .ply / .obj / .npy for meshes; .npy is not a mesh file, .off / .stl are read too
             input_list = [os.path.join(args.input_dir, x) for x in input_list if x.lower().endswith((".ply", ".obj", ".off", ".stl"))]
+        input_list = sorted(input_list + scans)              # --register_dist: a sub-directory is one object, its files its scans
     elif args.input_path is not None:
         input_list = [args.input_path]
     else:

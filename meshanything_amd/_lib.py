@@ -166,6 +166,10 @@ SIGNATURES = {
     "ma_op_pc_voxel_mark": (_I, [_P, C.c_uint64, _P, C.c_int64, _P, _P]),
     "ma_op_pc_align_extents": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_align_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "ma_op_pc_register_build": (_I, [_P, _I, _I, _P, _I, _I, _P, _F, _P, _P, C.c_size_t, _P]),
+    "ma_op_pc_register_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _F, _P, _P, _P, _F, _P, _I, C.c_uint64, _P, _P, C.POINTER(C.c_uint64), _P, _P,
+                                     C.c_size_t, _P]),
+    "ma_pc_register_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
 }
 
 _lib = None

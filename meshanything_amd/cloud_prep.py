@@ -8,7 +8,9 @@ Voxel thinning comes first because it is the only step that takes more than 2^22
 and every later step costs less on what it leaves.  The outlier statistic then sees an even density, which it assumes; strays survive
 thinning one per voxel while the surface loses most of its rows, so the strays' share of the cloud RISES and the outlier filter after it
 matters more, not less.  After the six, and before the pick, comes a step of its own kind, `POSE` (align_iters): it drops and adds no row but
-turns every kept part into the frame of its tightest box, and the part's keys gain "pose", with which the turn can be undone."""
+turns every kept part into the frame of its tightest box, and the part's keys gain "pose", with which the turn can be undone.  BEFORE the six
+comes another step of its own kind, `SCANS` (register_dist): an input that is a directory of partial scans becomes one cloud in the frame of
+its first scan (pc_register.register_rows); `data.Dataset` runs it, since it is the only step that takes several files."""
 from __future__ import annotations
 
 import importlib
@@ -97,6 +99,17 @@ def align(m, p, parts, n_points, device):
     return out
 
 
+def register(m, p, scans, names, uid, normal_k, device):
+    """register_dist=D: registration of the scans of one object, before anything else but each scan's own voxel thinning
+    (pc_register.register_rows, every scan >= 64 rows, the union <= 2^22, finite): scan 0 is the frame; scan j is moved onto the union of
+    the scans before it by at most register_iters (1..256) iterations of ICP with pairing distance D (file units), the point-to-plane
+    metric ("point": point-to-point) and the relative RMS tolerance register_tol (in [0, 1)); a scan of whose rows less than
+    register_min_overlap (in (0, 1]) end up paired is a ValueError.  -> (the merged rows, [(R, t)] float64 per scan).  Not one of STAGES: it
+    takes several files and runs before a file's rows exist."""
+    return m.register_rows(scans, p.register_dist, p.register_iters, p.register_tol, p.register_metric, p.register_min_overlap, normal_k, uid, device=device,
+                           names=names)
+
+
 def check_cluster(m, p, n_points):
     m.check_split_args(p.cluster_radius, p.cluster_min_points, p.cluster_mode)
     if p.cluster_min_points < p.floor(n_points):
@@ -121,6 +134,8 @@ STAGES = (                                                       # in the order 
     Stage("upsample_radius", "pc_upsample", lambda m, p, n: m.check_upsample_args(p.upsample_radius, p.upsample_target(n), n), upsample),
 )                                                                # then POSE, then the pick: the uniform draw, FPS, or the pc_xyz normal estimate (data.Dataset)
 POSE = Stage("align_iters", "pc_align", lambda m, p, n: m.check_align_args(p.align_iters, p.align_rounds, p.align_min_gain), align)
+SCANS = Stage("register_dist", "pc_register",
+              lambda m, p, n: m.check_register_args(p.register_dist, p.register_iters, p.register_tol, p.register_metric, p.register_min_overlap), register)
 
 
 @dataclass(frozen=True)
@@ -148,6 +163,11 @@ class CloudPrep:
     align_iters: int = 0
     align_rounds: int = 4
     align_min_gain: float = 0.02
+    register_dist: float = 0.0
+    register_iters: int = 30
+    register_tol: float = 1e-6
+    register_metric: str = "plane"
+    register_min_overlap: float = 0.3
 
     @classmethod
     def from_args(cls, args) -> "CloudPrep":
@@ -162,6 +182,10 @@ class CloudPrep:
         """[(POSE, its module)] if alignment is on, else []."""
         return [(POSE, importlib.import_module(f".{POSE.module}", __package__))] if self.align_iters else []
 
+    def scans(self):
+        """[(SCANS, its module)] if registration is on, else []."""
+        return [(SCANS, importlib.import_module(f".{SCANS.module}", __package__))] if self.register_dist else []
+
     def floor(self, n_points: int) -> int:
         """The fewest rows a file, and what a step leaves of it, may have."""
         return min(importlib.import_module(".pc_upsample", __package__).MIN_ROWS, n_points) if self.upsample_radius else n_points
@@ -170,14 +194,18 @@ class CloudPrep:
         return 4 * n_points if self.upsample_points is None else self.upsample_points
 
     def check(self, input_type: str, n_points: int) -> int:
-        """Everything that can be refused before a file is read, upsampling's options first, then in stage order, then alignment's -> the floor."""
+        """Everything that can be refused before a file is read, upsampling's options first, then in stage order, then alignment's, then registration's -> the floor."""
         if self.point_sampling not in ("random", "fps"):
             raise ValueError(f'point_sampling must be "random" or "fps", got {self.point_sampling!r}')
         if self.point_sampling == "fps" and input_type == "mesh":
             raise ValueError('point_sampling="fps" applies to pc_normal and pc_xyz inputs: the points of a mesh input are already drawn from its surface')
         if not self.upsample_radius and self.upsample_points is not None:
             raise ValueError("upsample_points needs upsample_radius > 0")
-        for stage, module in sorted(self.on(), key=lambda sm: sm[0].switch != "upsample_radius") + self.pose():
+        if not self.register_dist:
+            for f in fields(self):
+                if f.name.startswith("register_") and getattr(self, f.name) != f.default:
+                    raise ValueError(f"{f.name} needs register_dist > 0")
+        for stage, module in sorted(self.on(), key=lambda sm: sm[0].switch != "upsample_radius") + self.pose() + self.scans():
             if input_type == "mesh":
                 raise ValueError(f"{stage.switch} {stage.mesh}")
             stage.check(module, self, n_points)

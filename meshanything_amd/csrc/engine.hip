@@ -51,6 +51,7 @@
 #include "pc_align.hpp"
 #include "pc_plane.hpp"
 #include "pc_voxel.hpp"
+#include "pc_register.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1374,6 +1375,73 @@ int ma_op_pc_voxel_mark(void* table, uint64_t capacity, uint8_t* keep, int64_t N
         HIP_CHECK(pcv::launch_mark(table, capacity, keep, (uint64_t)N, s));
         HIP_CHECK(hipMemcpyAsync(state_out, pcv::state_of(table, capacity), pcv::STATE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+// ---- rigid registration: one ICP iteration of a source cloud onto a target cloud over the cell grid (csrc/pc_register.hpp) ------------------
+static_assert(MA_PC_REGISTER_SUMS == pcreg::SLOTS && MA_PC_REGISTER_THREADS == pcreg::THREADS && MA_PC_REGISTER_ROWS_PER_THREAD == pcreg::ROWS_PER_THREAD,
+              "the header's constants are the kernels'");
+static bool pc_register_shape_ok(int N, int M, int nx, int ny, int nz) { return pc_radius_shape_ok(N, nx, ny, nz) && M >= 1 && M <= MA_PC_GRID_MAX_POINTS; }
+
+size_t ma_pc_register_workspace_bytes(int N, int M, int nx, int ny, int nz) {
+    return pc_register_shape_ok(N, M, nx, ny, nz) ? pcreg::layout(N, M, nx * ny * nz).bytes : 0;
+}
+
+// the checks both calls share -> the grid
+static pcg::Grid register_grid(const std::string& op, const float* target, int N, int target_ld, const float* source, int M, int source_ld, const float* origin,
+                               float cell, const int32_t* dims, void* workspace, size_t workspace_bytes) {
+    if (!target || !source || !origin || !dims || !workspace) throw MaError(MA_ERR_INVALID, op + ": null pointer");
+    const pcg::Grid g = checked_grid(op, N >= 1 && N <= MA_PC_GRID_MAX_POINTS && M >= 1 && M <= MA_PC_GRID_MAX_POINTS, "1 <= N <= 2^22, 1 <= M <= 2^22", origin, cell, dims);
+    if ((target_ld != 3 && target_ld != 6) || (source_ld != 3 && source_ld != 6)) throw MaError(MA_ERR_INVALID, op + ": target_ld and source_ld must be 3 or 6");
+    if (workspace_bytes < pcreg::layout(N, M, pcg::cells_of(g)).bytes)
+        throw MaError(MA_ERR_INVALID, op + ": workspace smaller than ma_pc_register_workspace_bytes(N, M, nx, ny, nz)");
+    return g;
+}
+
+int ma_op_pc_register_build(const float* target, int N, int target_ld, const float* source, int M, int source_ld, const float* origin, float cell,
+                            const int32_t* dims, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        const pcg::Grid g = register_grid("ma_op_pc_register_build", target, N, target_ld, source, M, source_ld, origin, cell, dims, workspace, workspace_bytes);
+        HIP_CHECK(pcreg::launch_build(target, N, target_ld, source, M, source_ld, g, workspace, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_register_step(const float* target, int N, int target_ld, const float* source, int M, int source_ld, const float* origin, float cell,
+                           const int32_t* dims, const float* pose, const float* centre, float max_dist, const float* target_normals, int normals_ld,
+                           uint64_t max_pairs, int32_t* nn_idx, float* nn_d2, uint64_t* pair_bound, double* sums, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    return guarded(nullptr, [&] {
+        const std::string op = "ma_op_pc_register_step";
+        const pcg::Grid g = register_grid(op, target, N, target_ld, source, M, source_ld, origin, cell, dims, workspace, workspace_bytes);
+        if (!pose || !centre) throw MaError(MA_ERR_INVALID, op + ": null pointer");
+        if (!nn_idx && !nn_d2 && !sums) throw MaError(MA_ERR_INVALID, op + ": no output: give at least one of nn_idx, nn_d2 and sums");
+        if (target_normals && normals_ld < 3) throw MaError(MA_ERR_INVALID, op + ": normals_ld must be at least 3");
+        pcreg::Pose P;
+        for (int i = 0; i < 12; ++i) {
+            if (!std::isfinite(pose[i])) throw MaError(MA_ERR_INVALID, op + ": pose must be finite");
+            (i < 9 ? P.r[i] : P.t[i - 9]) = pose[i];
+        }
+        if (!std::isfinite(centre[0]) || !std::isfinite(centre[1]) || !std::isfinite(centre[2])) throw MaError(MA_ERR_INVALID, op + ": centre must be finite");
+        if (!std::isfinite(max_dist) || !(max_dist > 0.f)) throw MaError(MA_ERR_INVALID, op + ": max_dist must be finite and > 0");
+        if (!((double)max_dist / (double)g.cell <= (double)pcr::MAX_RINGS_RATIO)) throw MaError(MA_ERR_INVALID, op + ": max_dist / cell must be at most 8");
+        volatile float df = max_dist;
+        volatile float r2 = df * df;
+        if (!std::isfinite(r2)) throw MaError(MA_ERR_INVALID, op + ": max_dist * max_dist must be a finite float32");
+        const int R = pcr::rings(df, g.cell);
+        if (!pcr::rings_suffice(g, r2, R))
+            throw MaError(MA_ERR_INVALID, op + ": the float32 faces of this grid do not separate cells " + std::to_string(R) +
+                                              " apart by more than max_dist (origin too large against cell): the pair bound would not hold");
+        const uint64_t cap = max_pairs ? max_pairs : MA_PC_CLUSTER_MAX_PAIRS;
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        HIP_CHECK(pcreg::launch_bound(source, M, source_ld, P, N, g, R, workspace, s));
+        unsigned long long total = 0;
+        HIP_CHECK(hipMemcpyAsync(&total, pcreg::total_of(N, M, g, workspace), sizeof(total), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (pair_bound) *pair_bound = total;
+        if (total > cap)
+            throw MaError(MA_ERR_INVALID, op + ": the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
+                                              ": use a smaller max_dist or fewer points");
+        HIP_CHECK(pcreg::launch_step(target, N, target_ld, source, M, source_ld, P, centre, r2, g, target_normals, normals_ld, nn_idx, nn_d2, sums, workspace, s));
     });
 }
 

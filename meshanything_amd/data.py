@@ -44,6 +44,9 @@ def to_file_frame(verts: np.ndarray, frame, pose=None) -> np.ndarray:
     return verts
 
 
+SCAN_EXTENSIONS = {"pc_normal": (".npy", ".ply"), "pc_xyz": (".npy", ".xyz", ".txt", ".ply")}   # the point files of a directory of scans (register_dist)
+
+
 def uid_of(input_path: str) -> str:
     """main.py:27,39: the sample's name, the file name up to its first dot."""
     return input_path.split("/")[-1].split(".")[0]
@@ -68,20 +71,26 @@ class Dataset:
     hold up to 2^28; the outlier filter after it then sees an even density, in which the strays, kept one per voxel, have a larger share.
     After the six, on what they left and before the pick, align_iters (alignment to the tightest box, pc_align.py) turns every kept part into
     the frame in which its bounding box is smallest: `normalize_pc` and the decoder's lattice work along the axes, and a scan that sits askew
-    in its file wastes them.  Such an item carries "pose": (R', c), the turn and its fixed point."""
+    in its file wastes them.  Such an item carries "pose": (R', c), the turn and its fixed point.
+    Before all of them, register_dist (registration, pc_register.py) lets an entry of input_list be a DIRECTORY: one object, whose point files
+    (the type's extensions, in sorted order) are its partial scans and whose name is the uid.  Each scan is thinned on its own if voxel_size is
+    on, the scans are registered onto the first and merged, and the union then goes the way of a file's rows.  Such an item carries
+    "scan_poses": [(R, t)] float64, scan j's rows in the frame of scan 0 being R x + t.  A plain file passes through as without it."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
                  cluster_mode: str = "largest", cluster_min_points: int = 4096, plane_threshold: float = 0.0, plane_iters: int = 1024,
                  plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1,
                  upsample_radius: float = 0.0, upsample_points=None, voxel_size: float = 0.0, align_iters: int = 0, align_rounds: int = 4,
-                 align_min_gain: float = 0.02):
+                 align_min_gain: float = 0.02, register_dist: float = 0.0, register_iters: int = 30, register_tol: float = 1e-6,
+                 register_metric: str = "plane", register_min_overlap: float = 0.3):
         self.data: List[Dict] = []
         prep = CloudPrep(normal_k=normal_k, point_sampling=point_sampling, outlier_k=outlier_k, outlier_std=outlier_std, plane_threshold=plane_threshold,
                          plane_iters=plane_iters, plane_count=plane_count, plane_min_fraction=plane_min_fraction, cluster_radius=cluster_radius,
                          cluster_mode=cluster_mode, cluster_min_points=cluster_min_points, smooth_radius=smooth_radius, smooth_iters=smooth_iters,
                          upsample_radius=upsample_radius, upsample_points=upsample_points, voxel_size=voxel_size, align_iters=align_iters,
-                         align_rounds=align_rounds, align_min_gain=align_min_gain)
+                         align_rounds=align_rounds, align_min_gain=align_min_gain, register_dist=register_dist, register_iters=register_iters,
+                         register_tol=register_tol, register_metric=register_metric, register_min_overlap=register_min_overlap)
         floor = prep.check(input_type, n_points)                     # the fewest rows a file may have; every refusal that needs no file
         device = sample_device or "cuda"
 
@@ -100,7 +109,7 @@ class Dataset:
                 return load_ply_points(input_path, normals=True)
             return np.load(input_path)
 
-        def load_pc_xyz(input_path):
+        def load_pc_xyz(input_path, floor=floor):
             from . import pc_normals
             if input_path.lower().endswith(".ply"):
                 from .mesh_input import load_ply_points
@@ -115,10 +124,32 @@ class Dataset:
         def pick_pc_xyz(cur_data):
             from . import pc_normals
             return pc_normals.xyz_to_pc_normal(cur_data, n_points, normal_k, device=device, sampling=point_sampling)
+        def load_scans(input_path):
+            """A directory of partial scans -> (the merged rows, the uid, the scans' poses): cloud_prep.SCANS"""
+            (stage, module), = prep.scans()
+            uid = os.path.basename(os.path.normpath(input_path))
+            names = sorted(x for x in os.listdir(input_path) if x.lower().endswith(SCAN_EXTENSIONS[input_type]) and os.path.isfile(os.path.join(input_path, x)))
+            if not names:
+                raise ValueError(f"{uid}: the directory holds no {input_type} scan ({', '.join(SCAN_EXTENSIONS[input_type])})")
+            xyz = input_type == "pc_xyz"
+            scans = [load_pc_xyz(os.path.join(input_path, x), module.MIN_ROWS) if xyz else load_pc_normal(os.path.join(input_path, x)) for x in names]
+            if voxel_size:                                           # each scan on its own; the union is thinned again by the stage, where they overlap
+                from . import pc_voxel
+                scans = [pc_voxel.thin_rows(rows, voxel_size, module.MIN_ROWS, f"{uid}/{uid_of(x)}", device=device) for rows, x in zip(scans, names)]
+            merged, poses = stage.apply(module, prep, scans, [uid_of(x) for x in names], uid, normal_k if xyz else None, device)
+            if xyz:
+                from . import pc_normals
+                merged = pc_normals.check_xyz(merged, floor, normal_k)
+            return merged, uid, poses
         clouds = {"pc_normal": (load_pc_normal, pick_pc_normal), "pc_xyz": (load_pc_xyz, pick_pc_xyz)}   # how a file is loaded, how its n_points rows are picked
         if input_type in clouds:
             load, pick = clouds[input_type]
             for input_path in input_list:
+                if register_dist and os.path.isdir(input_path):
+                    rows, uid, poses = load_scans(input_path)
+                    for cur_data, keys in prep.parts(rows, uid, device, n_points):
+                        self.data.append({"pc_normal": pick(cur_data), **keys, "scan_poses": poses})
+                    continue
                 for cur_data, keys in prep.parts(load(input_path), uid_of(input_path), device, n_points):
                     self.data.append({"pc_normal": pick(cur_data), **keys})
         elif input_type == "mesh":
@@ -164,4 +195,6 @@ class Dataset:
             item.update(group=d["group"], part=d["part"], frame=pc_frame(d["pc_normal"]))
         if "pose" in d:
             item["pose"] = d["pose"]
+        if "scan_poses" in d:
+            item["scan_poses"] = d["scan_poses"]
         return item
