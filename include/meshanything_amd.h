@@ -891,6 +891,58 @@ MA_API int    ma_op_pc_register_step(const float *target, int N, int target_ld, 
                                      void *workspace, size_t workspace_bytes, void *stream);
 MA_API size_t ma_pc_register_workspace_bytes(int N, int M, int nx, int ny, int nz);
 
+/* ---- Coarse registration from unknown poses, for --coarse_radius (csrc/pc_coarse.hpp): PCL's FPFHEstimation and
+ * SampleConsensusPrerejective, Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching do the same job.  Has no
+ * reference counterpart.  Needs no engine; errors via ma_last_error(NULL); every argument is checked before the first HIP call.  Device
+ * arrays (origin, dims, pair_bound and most_used are HOST pointers).  Each op is a pure function of its inputs, and its integer outputs
+ * equal a numpy float32 restatement byte for byte: no FMA contraction, IEEE sqrt and /, no floating-point atomics.
+ *
+ * ma_op_pc_spfh: ref (N, ref_ld) fp32, xyz in the first three columns, ref_ld = 3 or 6; normals: row i at normals + i * normals_ld, fp32,
+ *   normals_ld >= 3 (pass ref + 3 with ld 6 for a cloud that carries its normals); the grid as for ma_op_pc_cluster, radius / cell <= 8.
+ *   NOT asynchronous: it reads the pair bound back before the search, as ma_op_pc_cluster does (same guard, same max_pairs, same
+ *   refusal), and the largest number of used pairs after it.  r2 = fl32(radius * radius).  For row p with position x_p and normal n_p
+ *   the NEIGHBOURS are the rows q with 0 < d <= r2, d = fl32(fl32(dx*dx + dy*dy) + dz*dz), dx = fl32(x_p.x - x_q.x), ...: the key of
+ *   ma_op_pc_knn; equality with r2 is included, a NaN key is no neighbour, d = 0 (the row itself, a duplicate) has no direction.  Per pair
+ *       dot(u, v) = fl32(fl32(fl32(u_x*v_x) + fl32(u_y*v_y)) + fl32(u_z*v_z)),  len = fl32(sqrt(d)),  D = (dx, dy, dz)
+ *       a = fl32(|dot(n_p, D)| / len)   b = fl32(|dot(n_q, D)| / len)   c = |dot(n_p, n_q)|
+ *       bin(v) = 10 if fl32(v * 11) >= 10, else (int)fl32(v * 11)
+ *   hist (N, MA_PC_SPFH_COLS) uint32, row p: [0..10] the counts of bin(a), [11..21] of bin(b), [22..32] of bin(c), [33] the pairs used.
+ *   A pair is skipped and counted nowhere when either normal has a non-finite component or is (0, 0, 0), or when a, b or c is NaN.  The
+ *   features carry no sign: a scan's estimated normals are unoriented.  *most_used (if given) = the largest [33] if it is above
+ *   MA_PC_SPFH_MAX_USED, else 0; above it the call fails with MA_ERR_INVALID (thin the cloud or use a smaller radius) and hist is not
+ *   to be used: under that limit the sums of the gather cannot overflow.
+ * ma_op_pc_spfh_gather: the same cloud, radius and grid; hist as above; query (Q) int32, 1 <= Q <= MA_PC_SPFH_MAX_QUERIES, repeats allowed.
+ *   desc (Q, MA_PC_SPFH_DESC) uint32, desc[j] = hist[p] + sum over the neighbours q of p = query[j] (0 < d <= r2, nothing else) of hist[q],
+ *   columns 0..32, modulo 2^32; a query outside [0, N) gives a zero row.  FPFH's second pass without the 1/d weights: integer sums need
+ *   no order.  Builds the grid itself and applies the same guard; NOT asynchronous.
+ * workspace of both: ma_pc_spfh_workspace_bytes(N, nx, ny, nz) bytes of device memory (0 outside the limits); its contents do not matter.
+ * ma_op_pc_desc_match: A (Ka, 33), B (Kb, 33) uint32, 1 <= Ka, Kb <= MA_PC_COARSE_MAX_KEYPOINTS.  Every block of 11 is normalised by its
+ *   integer sum S: x = fl32(fl32(h) / fl32(S)), a zero block stays zero; dist = the SEQUENTIAL fp32 sum over bins 0..32, from 0, of
+ *   fl32(fl32(x - y) * fl32(x - y)).  idx (Ka) int32 = the row of B least in (dist, index), dist (Ka, or NULL) fp32 = that distance.  Asynchronous.
+ * ma_op_pc_pose_score: poses (H, 12) fp32, R row-major then t, 1 <= H <= MA_PC_COARSE_MAX_HYPOTHESES; P, Q (C, 3) fp32 contiguous, 1 <= C <=
+ *   MA_PC_COARSE_MAX_KEYPOINTS; t2 = fl32(max_dist * max_dist).  counts (H) int32 = the number of pairs i whose key between p' (the
+ *   transform of ma_op_pc_register_step applied to P_i, rounding for rounding) and Q_i is <= t2; a NaN key agrees with nothing.  best (1,
+ *   or NULL) int32 = the h of the highest count, the lowest index among equals (ma_op_pc_plane_score's rule).  Asynchronous. */
+#define MA_PC_SPFH_BINS             11
+#define MA_PC_SPFH_DESC             33
+#define MA_PC_SPFH_COLS             34
+#define MA_PC_SPFH_MAX_USED         65535
+#define MA_PC_SPFH_MAX_QUERIES      (1 << 20)
+#define MA_PC_COARSE_MAX_KEYPOINTS  4096
+#define MA_PC_COARSE_MAX_HYPOTHESES (1 << 16)
+MA_API int    ma_op_pc_spfh(const float *ref, int N, int ref_ld, const float *normals, int normals_ld, float radius, const float *origin,
+                            float cell, const int32_t *dims, uint64_t max_pairs /* 0 = MA_PC_CLUSTER_MAX_PAIRS */, uint32_t *hist,
+                            uint64_t *pair_bound /* host pointer or NULL */, uint32_t *most_used /* host pointer or NULL */, void *workspace,
+                            size_t workspace_bytes, void *stream);
+MA_API int    ma_op_pc_spfh_gather(const float *ref, int N, int ref_ld, float radius, const float *origin, float cell, const int32_t *dims,
+                                   uint64_t max_pairs /* 0 = MA_PC_CLUSTER_MAX_PAIRS */, const uint32_t *hist, const int32_t *query, int Q,
+                                   uint32_t *desc, uint64_t *pair_bound /* host pointer or NULL */, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+MA_API size_t ma_pc_spfh_workspace_bytes(int N, int nx, int ny, int nz);
+MA_API int    ma_op_pc_desc_match(const uint32_t *A, int Ka, const uint32_t *B, int Kb, int32_t *idx, float *dist /* or NULL */, void *stream);
+MA_API int    ma_op_pc_pose_score(const float *poses, int H, const float *P, const float *Q, int C, float max_dist, int32_t *counts,
+                                  int32_t *best /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

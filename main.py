@@ -77,7 +77,19 @@ for clouds without usable normals; pc_xyz scans get normals from `--normal_k` ne
 times (default 30, 1..256) or until the RMS changes by at most `--register_tol` of itself (default 1e-6, in [0, 1)).  The scans must start
 within D of their place: a scan of whose points less than `--register_min_overlap` (default 0.3, in (0, 1]) find a partner is an error, not
 a guess.  With `--voxel_size` each scan is thinned before, and the union again after, where overlapping scans doubled the density.  One
-line per scan reports iterations, the paired share, the RMS and the motion.  No global (featureless) alignment, no loop closure.
+line per scan reports iterations, the paired share, the RMS and the motion.  No loop closure.
+`--coarse_radius F` (with `--register_dist`; 0 = off, the default; in the units of the input files) is for scans in UNKNOWN poses -- a
+turntable without an encoder, a hand-held scanner, files exported one by one: every scan's ICP then starts not from the file's frame but
+from a coarse pose found on the GPU (`meshanything_amd/pc_coarse.py`).  `--coarse_points` (default 1024, 64..4096) farthest-point keypoints
+are picked on the scan and on the union before it; every point gets a histogram of three angle features over the points within F of it
+(PCL's and Open3D's FPFH without the signs, which unoriented normals do not have, and without distance weights, so that it is integer and
+exact), summed once more over the same neighbourhood at the keypoints; the descriptors are matched both ways and the mutual matches kept;
+`--coarse_iters` (default 4096, 256..65536) triples of matches from a private generator, less those whose triangles do not match in edge
+length, each give a pose, and the pose with which the most matches land within `--coarse_dist` (default F / 4) of their partner wins and is
+refitted to them.  F should span several point spacings and a fraction of the object.  One more line per scan reports the matches, the
+surviving triples, the agreeing matches and the turn.  Too few matches or agreeing pairs is an error, not a guess.  Out of its reach: a
+solid of large flat faces, whose descriptors all look alike, and a nearly symmetric one, whose half-turn twin overlaps as well as the truth
+-- no overlap check can tell them apart.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -104,6 +116,8 @@ STEP_FLAGS = (
     ("align_iters", {"align_rounds": (4, lambda v: 0 <= v <= 8, "in 0..8"), "align_min_gain": (0.02, lambda v: 0.0 <= v < 1.0, "in [0, 1)")}),
     ("register_dist", {"register_iters": (30, lambda v: 1 <= v <= 256, "in 1..256"), "register_tol": (1e-6, lambda v: 0.0 <= v < 1.0, "in [0, 1)"),
                        "register_metric": ("plane", None, None), "register_min_overlap": (0.3, lambda v: 0.0 < v <= 1.0, "in (0, 1]")}),
+    ("coarse_radius", {"coarse_points": (1024, lambda v: 64 <= v <= 4096, "in 64..4096"), "coarse_iters": (4096, lambda v: 256 <= v <= 65536, "in 256..65536"),
+                       "coarse_dist": (None, lambda v: 0.0 < v < float("inf"), "finite and > 0")}),       # its need of --register_dist: after the table
 )
 
 
@@ -192,6 +206,14 @@ def get_args(argv=None):
                    help="with --register_dist: point-to-plane distances (the default) or point-to-point, for clouds without usable normals")
     p.add_argument("--register_min_overlap", default=None, type=float,
                    help="with --register_dist: refuse a scan of whose points less than this fraction find a partner (in (0, 1], default 0.3)")
+    p.add_argument("--coarse_radius", default=0.0, type=float,
+                   help="with --register_dist: the scans are in UNKNOWN poses: start every scan's ICP from a pose found on the GPU by matching feature "
+                        "histograms over the points within this distance of each keypoint, in the units of the input files: several point spacings, "
+                        "a fraction of the object (0 = off).  Large flat faces and near-symmetric objects are out of its reach")
+    p.add_argument("--coarse_points", default=None, type=int, help="with --coarse_radius: farthest-point keypoints per cloud (64..4096, default 1024)")
+    p.add_argument("--coarse_iters", default=None, type=int, help="with --coarse_radius: pose hypotheses, each from three matches (256..65536, default 4096)")
+    p.add_argument("--coarse_dist", default=None, type=float,
+                   help="with --coarse_radius: a matched pair agrees with a hypothesis when it lands within this distance (default --coarse_radius / 4)")
     args = p.parse_args(argv)
     for switch, others in STEP_FLAGS:
         flags = [f"--{name}" for name in (switch, *others)]
@@ -207,6 +229,8 @@ def get_args(argv=None):
                 setattr(args, name, default)
             elif ok is not None and not ok(getattr(args, name)):
                 p.error(f"--{name} must be {wording}")
+    if args.coarse_radius > 0 and args.register_dist == 0:
+        p.error("--coarse_radius needs --register_dist > 0: the coarse pose is where a scan's registration starts")
     if args.align_iters != 0 and not 256 <= args.align_iters <= 65536:
         p.error("--align_iters must be 0 (off) or in 256..65536")
     if args.upsample_radius > 0 and args.cluster_min_points < 64:            # the default passes both

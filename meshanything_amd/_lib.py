@@ -170,6 +170,11 @@ SIGNATURES = {
     "ma_op_pc_register_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _F, _P, _P, _P, _F, _P, _I, C.c_uint64, _P, _P, C.POINTER(C.c_uint64), _P, _P,
                                      C.c_size_t, _P]),
     "ma_pc_register_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "ma_op_pc_spfh": (_I, [_P, _I, _I, _P, _I, _F, _P, _F, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _P, C.c_size_t, _P]),
+    "ma_op_pc_spfh_gather": (_I, [_P, _I, _I, _F, _P, _F, _P, C.c_uint64, _P, _P, _I, _P, C.POINTER(C.c_uint64), _P, C.c_size_t, _P]),
+    "ma_pc_spfh_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "ma_op_pc_desc_match": (_I, [_P, _I, _P, _I, _P, _P, _P]),
+    "ma_op_pc_pose_score": (_I, [_P, _I, _P, _P, _I, _F, _P, _P, _P]),
 }
 
 _lib = None

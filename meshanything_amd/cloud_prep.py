@@ -10,7 +10,8 @@ thinning one per voxel while the surface loses most of its rows, so the strays' 
 matters more, not less.  After the six, and before the pick, comes a step of its own kind, `POSE` (align_iters): it drops and adds no row but
 turns every kept part into the frame of its tightest box, and the part's keys gain "pose", with which the turn can be undone.  BEFORE the six
 comes another step of its own kind, `SCANS` (register_dist): an input that is a directory of partial scans becomes one cloud in the frame of
-its first scan (pc_register.register_rows); `data.Dataset` runs it, since it is the only step that takes several files."""
+its first scan (pc_register.register_rows); `data.Dataset` runs it, since it is the only step that takes several files.  coarse_radius is an
+option OF that step, not a stage: with it every scan's registration starts from a pose found by pc_coarse.coarse_pose, for scans in unknown poses."""
 from __future__ import annotations
 
 import importlib
@@ -105,9 +106,15 @@ def register(m, p, scans, names, uid, normal_k, device):
     the scans before it by at most register_iters (1..256) iterations of ICP with pairing distance D (file units), the point-to-plane
     metric ("point": point-to-point) and the relative RMS tolerance register_tol (in [0, 1)); a scan of whose rows less than
     register_min_overlap (in (0, 1]) end up paired is a ValueError.  -> (the merged rows, [(R, t)] float64 per scan).  Not one of STAGES: it
-    takes several files and runs before a file's rows exist."""
-    return m.register_rows(scans, p.register_dist, p.register_iters, p.register_tol, p.register_metric, p.register_min_overlap, normal_k, uid, device=device,
-                           names=names)
+    takes several files and runs before a file's rows exist.
+    coarse_radius=F (file units) on top of it: scans in UNKNOWN poses.  Scan j's ICP then starts from `pc_coarse.coarse_pose` against the union:
+    coarse_points (64..4096) farthest-point keypoints a cloud, a feature histogram over the rows within F of each, matched both ways, and
+    coarse_iters (256..65536) triples of matches scored by the matches within coarse_dist (None = F / 4) of where the triple's pose puts them.
+    Off, `register_rows` gets exactly the call it got before the stage existed."""
+    args = (scans, p.register_dist, p.register_iters, p.register_tol, p.register_metric, p.register_min_overlap, normal_k, uid)
+    if not p.coarse_radius:
+        return m.register_rows(*args, device=device, names=names)
+    return m.register_rows(*args, device=device, names=names, coarse=(p.coarse_radius, p.coarse_points, p.coarse_iters, p.coarse_dist))
 
 
 def check_cluster(m, p, n_points):
@@ -168,6 +175,10 @@ class CloudPrep:
     register_tol: float = 1e-6
     register_metric: str = "plane"
     register_min_overlap: float = 0.3
+    coarse_radius: float = 0.0
+    coarse_points: int = 1024
+    coarse_iters: int = 4096
+    coarse_dist: Optional[float] = None
 
     @classmethod
     def from_args(cls, args) -> "CloudPrep":
@@ -205,6 +216,16 @@ class CloudPrep:
             for f in fields(self):
                 if f.name.startswith("register_") and getattr(self, f.name) != f.default:
                     raise ValueError(f"{f.name} needs register_dist > 0")
+        for f in fields(self):
+            if f.name.startswith("coarse_") and getattr(self, f.name) != f.default:
+                if input_type == "mesh":
+                    raise ValueError(f"{f.name} applies to the scans of pc_normal and pc_xyz inputs, not to mesh inputs")
+                if not self.coarse_radius:
+                    raise ValueError(f"{f.name} needs coarse_radius > 0")
+                if not self.register_dist:
+                    raise ValueError(f"{f.name} needs register_dist > 0: the coarse pose is where a scan's registration starts")
+        if self.coarse_radius:
+            importlib.import_module(".pc_coarse", __package__).check_coarse_args(self.coarse_radius, self.coarse_points, self.coarse_iters, self.coarse_dist)
         for stage, module in sorted(self.on(), key=lambda sm: sm[0].switch != "upsample_radius") + self.pose() + self.scans():
             if input_type == "mesh":
                 raise ValueError(f"{stage.switch} {stage.mesh}")

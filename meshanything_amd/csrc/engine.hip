@@ -52,6 +52,7 @@
 #include "pc_plane.hpp"
 #include "pc_voxel.hpp"
 #include "pc_register.hpp"
+#include "pc_coarse.hpp"
 // MA_EXPERIMENTAL (build.py: MA_EXPERIMENTAL=1): the measured-and-rejected decode-step forms -- the persistent one-launch step
 // (persist.hpp), the rows-looped two-launch layer (rows_fused.hpp) and the layer-pair launch (layer_fused.hpp); DESIGN.md records why
 // each lost.  They are evidence, not product: the shipped library does not contain them, their tests skip without the flag.
@@ -1442,6 +1443,77 @@ int ma_op_pc_register_step(const float* target, int N, int target_ld, const floa
             throw MaError(MA_ERR_INVALID, op + ": the pair bound " + std::to_string(total) + " exceeds max_pairs " + std::to_string(cap) +
                                               ": use a smaller max_dist or fewer points");
         HIP_CHECK(pcreg::launch_step(target, N, target_ld, source, M, source_ld, P, centre, r2, g, target_normals, normals_ld, nn_idx, nn_d2, sums, workspace, s));
+    });
+}
+
+// ---- coarse registration from unknown poses: feature histograms, their second pass, matching and hypothesis scoring (csrc/pc_coarse.hpp) ------
+static_assert(MA_PC_SPFH_BINS == pcf::BINS && MA_PC_SPFH_DESC == pcf::DESC && MA_PC_SPFH_COLS == pcf::COLS && MA_PC_SPFH_MAX_USED == pcf::MAX_USED &&
+                  MA_PC_SPFH_MAX_QUERIES == pcf::MAX_QUERIES && MA_PC_COARSE_MAX_KEYPOINTS == pcf::MAX_KEYPOINTS &&
+                  MA_PC_COARSE_MAX_HYPOTHESES == pcf::MAX_HYPOTHESES,
+              "the header's constants are the kernels'");
+
+size_t ma_pc_spfh_workspace_bytes(int N, int nx, int ny, int nz) { return pc_radius_shape_ok(N, nx, ny, nz) ? pcf::layout(N, nx * ny * nz).bytes : 0; }
+
+int ma_op_pc_spfh(const float* ref, int N, int ref_ld, const float* normals, int normals_ld, float radius, const float* origin, float cell,
+                  const int32_t* dims, uint64_t max_pairs, uint32_t* hist, uint64_t* pair_bound, uint32_t* most_used, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !normals || !origin || !dims || !hist || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh: null pointer");
+        const pcg::Grid g = radius_grid("ma_op_pc_spfh", N, origin, cell, dims);
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh: ref_ld must be 3 or 6");
+        if (normals_ld < 3) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh: normals_ld must be at least 3");
+        if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh: radius must be finite and > 0");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        const float r2 = radius_prologue("spfh", "radius", ref, N, ref_ld, g, (double)radius, max_pairs, workspace, workspace_bytes,
+                                         pcf::layout(N, pcg::cells_of(g)).bytes, pair_bound, nullptr, s);
+        HIP_CHECK(pcf::launch_spfh(N, normals, normals_ld, r2, g, hist, workspace, s));
+        unsigned most = 0;
+        HIP_CHECK(hipMemcpyAsync(&most, pcf::most_of(N, g, workspace), sizeof(most), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (most_used) *most_used = most;
+        if (most > pcf::MAX_USED)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh: a row has " + std::to_string(most) + " neighbours, more than " + std::to_string(pcf::MAX_USED) +
+                                              ": thin the cloud (--voxel_size) or use a smaller radius");
+    });
+}
+
+int ma_op_pc_spfh_gather(const float* ref, int N, int ref_ld, float radius, const float* origin, float cell, const int32_t* dims, uint64_t max_pairs,
+                         const uint32_t* hist, const int32_t* query, int Q, uint32_t* desc, uint64_t* pair_bound, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    return guarded(nullptr, [&] {
+        if (!ref || !origin || !dims || !hist || !query || !desc || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh_gather: null pointer");
+        const pcg::Grid g = radius_grid("ma_op_pc_spfh_gather", N, origin, cell, dims);
+        if (ref_ld != 3 && ref_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh_gather: ref_ld must be 3 or 6");
+        if (Q < 1 || Q > MA_PC_SPFH_MAX_QUERIES) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh_gather: need 1 <= Q <= 2^20");
+        if (!std::isfinite(radius) || !(radius > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh_gather: radius must be finite and > 0");
+        if (workspace_bytes < pcf::layout(N, pcg::cells_of(g)).bytes)      // the one workspace of both passes: the prologue's wording would name no function
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_spfh_gather: workspace smaller than ma_pc_spfh_workspace_bytes(N, nx, ny, nz)");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        const float r2 = radius_prologue("spfh_gather", "radius", ref, N, ref_ld, g, (double)radius, max_pairs, workspace, workspace_bytes,
+                                         pcf::layout(N, pcg::cells_of(g)).bytes, pair_bound, nullptr, s);
+        HIP_CHECK(pcf::launch_gather(ref, N, ref_ld, r2, g, hist, query, Q, desc, workspace, s));
+    });
+}
+
+int ma_op_pc_desc_match(const uint32_t* A, int Ka, const uint32_t* B, int Kb, int32_t* idx, float* dist, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!A || !B || !idx) throw MaError(MA_ERR_INVALID, "ma_op_pc_desc_match: null pointer");
+        if (Ka < 1 || Ka > MA_PC_COARSE_MAX_KEYPOINTS || Kb < 1 || Kb > MA_PC_COARSE_MAX_KEYPOINTS)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_desc_match: need 1 <= Ka, Kb <= 4096");
+        HIP_CHECK(pcf::launch_match(A, Ka, B, Kb, idx, dist, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int ma_op_pc_pose_score(const float* poses, int H, const float* P, const float* Q, int C, float max_dist, int32_t* counts, int32_t* best, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!poses || !P || !Q || !counts) throw MaError(MA_ERR_INVALID, "ma_op_pc_pose_score: null pointer");
+        if (H < 1 || H > MA_PC_COARSE_MAX_HYPOTHESES || C < 1 || C > MA_PC_COARSE_MAX_KEYPOINTS)
+            throw MaError(MA_ERR_INVALID, "ma_op_pc_pose_score: need 1 <= H <= 2^16 and 1 <= C <= 4096");
+        if (!std::isfinite(max_dist) || !(max_dist > 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_pc_pose_score: max_dist must be finite and > 0");
+        volatile float tf = max_dist;
+        volatile float t2 = tf * tf;
+        if (!std::isfinite(t2)) throw MaError(MA_ERR_INVALID, "ma_op_pc_pose_score: max_dist * max_dist must be a finite float32");
+        HIP_CHECK(pcf::launch_score(poses, H, P, Q, C, t2, counts, best, reinterpret_cast<hipStream_t>(stream)));
     });
 }
 

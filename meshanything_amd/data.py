@@ -75,7 +75,9 @@ class Dataset:
     Before all of them, register_dist (registration, pc_register.py) lets an entry of input_list be a DIRECTORY: one object, whose point files
     (the type's extensions, in sorted order) are its partial scans and whose name is the uid.  Each scan is thinned on its own if voxel_size is
     on, the scans are registered onto the first and merged, and the union then goes the way of a file's rows.  Such an item carries
-    "scan_poses": [(R, t)] float64, scan j's rows in the frame of scan 0 being R x + t.  A plain file passes through as without it."""
+    "scan_poses": [(R, t)] float64, scan j's rows in the frame of scan 0 being R x + t.  A plain file passes through as without it.
+    coarse_radius (with register_dist; pc_coarse.py) is for scans in UNKNOWN poses: every scan's ICP starts from a pose found by matching
+    feature histograms over that radius at coarse_points keypoints and scoring coarse_iters triples of matches within coarse_dist."""
 
     def __init__(self, input_type: str, input_list: List[str], mc: bool = False, n_points: int = 4096, sample_device=None, normal_k: int = 16,
                  point_sampling: str = "random", outlier_k: int = 0, outlier_std: float = 2.0, cluster_radius: float = 0.0,
@@ -83,14 +85,16 @@ class Dataset:
                  plane_count: int = 1, plane_min_fraction: float = 0.2, smooth_radius: float = 0.0, smooth_iters: int = 1,
                  upsample_radius: float = 0.0, upsample_points=None, voxel_size: float = 0.0, align_iters: int = 0, align_rounds: int = 4,
                  align_min_gain: float = 0.02, register_dist: float = 0.0, register_iters: int = 30, register_tol: float = 1e-6,
-                 register_metric: str = "plane", register_min_overlap: float = 0.3):
+                 register_metric: str = "plane", register_min_overlap: float = 0.3, coarse_radius: float = 0.0, coarse_points: int = 1024,
+                 coarse_iters: int = 4096, coarse_dist=None):
         self.data: List[Dict] = []
         prep = CloudPrep(normal_k=normal_k, point_sampling=point_sampling, outlier_k=outlier_k, outlier_std=outlier_std, plane_threshold=plane_threshold,
                          plane_iters=plane_iters, plane_count=plane_count, plane_min_fraction=plane_min_fraction, cluster_radius=cluster_radius,
                          cluster_mode=cluster_mode, cluster_min_points=cluster_min_points, smooth_radius=smooth_radius, smooth_iters=smooth_iters,
                          upsample_radius=upsample_radius, upsample_points=upsample_points, voxel_size=voxel_size, align_iters=align_iters,
                          align_rounds=align_rounds, align_min_gain=align_min_gain, register_dist=register_dist, register_iters=register_iters,
-                         register_tol=register_tol, register_metric=register_metric, register_min_overlap=register_min_overlap)
+                         register_tol=register_tol, register_metric=register_metric, register_min_overlap=register_min_overlap,
+                         coarse_radius=coarse_radius, coarse_points=coarse_points, coarse_iters=coarse_iters, coarse_dist=coarse_dist)
         floor = prep.check(input_type, n_points)                     # the fewest rows a file may have; every refusal that needs no file
         device = sample_device or "cuda"
 

@@ -9,7 +9,8 @@ so that they are the same on every run.  The rest is host numpy in float64: `sol
 faces do not resist sliding along themselves), `solve_point` (Kabsch, for clouds without usable normals), `compose`, the loop `icp` over a
 callable pose -> sums, and `register_rows`, which `data.Dataset` calls.  The poses are composed in float64 and applied to the ORIGINAL
 source rows every time, so no error accumulates in the points.  It needs CUDA tensors; there is no CPU fallback.  There is no reference
-counterpart.  Out of scope: global (featureless) alignment, loop closure, colour, non-rigid motion, mesh inputs.
+counterpart.  Scans in unknown poses: `register_rows(..., coarse=...)` puts `pc_coarse.coarse_pose` in front of every scan's ICP
+(`--coarse_radius`).  Out of scope: loop closure, colour, non-rigid motion, mesh inputs.
 """
 from __future__ import annotations
 
@@ -264,14 +265,21 @@ def scan_normals(cloud: torch.Tensor, k: int) -> torch.Tensor:
 
 
 def register_rows(scans, dist, iters: int = 30, tol: float = 1e-6, metric: str = "plane", min_overlap: float = 0.3, normal_k=None, uid: str = "?", device="cuda",
-                  names=None):
+                  names=None, coarse=None):
     """scans: host arrays (N_j, >= 3) of one object, all with the same number of columns, each of >= 64 finite rows -> (the merged rows,
     [(R_j, t_j)] float64).  Scan 0 is the frame, (I, 0).  Scan j is registered by `icp` onto the UNION of scans 0 .. j - 1 as registered
     (float32), from the identity, then appended: xyz -> R x + t in float64, cast to the scans' dtype.  normal_k None: columns 3:6 are the
     scans' normals (pc_normal), they serve the plane metric and are turned by R in the merged rows.  normal_k = k (pc_xyz): the plane
     metric's normals are estimated per scan, once, on that scan alone (`scan_normals`) and turned with it; no column but xyz changes.
-    The union may hold at most 2^22 rows.  Prints one line per scan.  Makes no draw from any RNG."""
+    The union may hold at most 2^22 rows.  Prints one line per scan.  Makes no draw from any RNG.
+    coarse: None, or (radius, points, iters, dist) as `pc_coarse.check_coarse_args` takes them: scan j then starts ICP not from the identity
+    but from `pc_coarse.coarse_pose` of the scan against the union, for scans in unknown poses.  That takes normals on both sides whatever
+    the metric, so every scan's are estimated (or read) and none is skipped; it prints a second line per scan, and its triples come from a
+    generator of its own, not from the numpy RNG."""
     dist, iters, tol, metric, min_overlap = check_register_args(dist, iters, tol, metric, min_overlap)
+    if coarse is not None:
+        from . import pc_coarse
+        coarse = pc_coarse.check_coarse_args(*coarse)
     scans = [as_host_cloud(s) for s in scans]
     names = [str(j) for j in range(len(scans))] if names is None else list(names)
     if not scans or len(names) != len(scans):
@@ -284,17 +292,20 @@ def register_rows(scans, dist, iters: int = 30, tol: float = 1e-6, metric: str =
         check_finite(s)
     if normal_k is None and metric == "plane" and scans[0].shape[1] < 6:
         raise ValueError(f"{uid}: the plane metric needs normals in columns 3:6, or normal_k to estimate them")
+    if normal_k is None and coarse is not None and scans[0].shape[1] < 6:
+        raise ValueError(f"{uid}: coarse registration needs normals in columns 3:6, or normal_k to estimate them")
     total = sum(s.shape[0] for s in scans)
     if total > MAX_POINTS:
         raise ValueError(f"{uid}: the union of the scans has {total} rows, more than 2^22: thin the scans with --voxel_size")
     dev = cuda_device(device, "register_rows")
     plane = metric == "plane"
+    normals = plane or coarse is not None                            # whether the device clouds carry normals in columns 3:6
     poses, merged = [IDENTITY], [scans[0].copy()]
     print(f"{uid}: registration (distance {dist:g}, {metric} metric): scan {names[0]} is the frame, {scans[0].shape[0]} rows")
     with torch.cuda.device(dev):
         def device_scan(s):
             xyz = torch.from_numpy(np.ascontiguousarray(s[:, :3], dtype=np.float32)).to(dev)
-            if not plane:
+            if not normals:
                 return xyz
             n = scan_normals(xyz, normal_k) if normal_k is not None else torch.from_numpy(np.ascontiguousarray(s[:, 3:6], dtype=np.float32)).to(dev)
             return torch.cat([xyz, n], 1)
@@ -303,11 +314,19 @@ def register_rows(scans, dist, iters: int = 30, tol: float = 1e-6, metric: str =
         for j in range(1, len(scans)):
             s = scans[j]
             last = j == len(scans) - 1
-            source = device_scan(s) if plane and not (last and normal_k is not None) else torch.from_numpy(np.ascontiguousarray(s[:, :3], dtype=np.float32)).to(dev)
+            skip = last and normal_k is not None and coarse is None     # the last scan's estimated normals would serve nothing
+            source = device_scan(s) if normals and not skip else torch.from_numpy(np.ascontiguousarray(s[:, :3], dtype=np.float32)).to(dev)
             centre = s[:, :3].astype(np.float64).mean(0).astype(np.float32)
+            start = IDENTITY
+            if coarse is not None:
+                tgt, src = union.cpu().numpy(), source.cpu().numpy()
+                found = pc_coarse.coarse_pose(tgt[:, :3], tgt[:, 3:6], src[:, :3], src[:, 3:6], *coarse, ops=pc_coarse.DeviceOps(dev), scan=names[j], uid=uid)
+                start = found["pose"]
+                print(f"{uid}: scan {names[j]}: coarse pose from {found['mutual']} matches, {found['triples']} triples, {found['count']} agreeing, "
+                      f"turned {found['angle']:.4g} degrees")
             built = build(union, source, dist)
             res = icp(lambda p: icp_step(built, pose12(p), centre, dist, "target" if plane else None)["sums"].cpu().numpy(), centre.astype(np.float64), s.shape[0],
-                      iters, tol, metric, min_overlap, names[j], uid)
+                      iters, tol, metric, min_overlap, names[j], uid, pose=start)
             R, t = res["pose"]
             poses.append((R, t))
             merged.append(apply_pose(s, (R, t), normals=normal_k is None))
@@ -316,7 +335,7 @@ def register_rows(scans, dist, iters: int = 30, tol: float = 1e-6, metric: str =
                   f"{res['rms_last']:.6g}, turned {angle:.4g} degrees, moved {float(np.linalg.norm(t)):.6g}")
             if not last:                                             # the union grows by the scan as registered: float64 on the host, then cast
                 moved = (s[:, :3].astype(np.float64) @ R.T + t).astype(np.float32)
-                if plane:
+                if normals:
                     moved = np.concatenate([moved, (source[:, 3:6].cpu().numpy().astype(np.float64) @ R.T).astype(np.float32)], 1)
                 union = torch.cat([union, torch.from_numpy(moved).to(dev)])
     return np.concatenate(merged), poses
