@@ -514,6 +514,39 @@ MA_API int    ma_op_mesh_normals(const float *coords, int B, int F, const float 
                                  float *face_agree, float *nscores, void *workspace, size_t ws_bytes, void *stream);
 MA_API size_t ma_mesh_normals_workspace_bytes(int B, int F);
 
+/* ---- fit of a generated mesh to the cloud it was generated from (csrc/mesh_fit.hpp; --fit_iters): one pairing of the cloud's points with
+ * the mesh's faces and the per-face sums of the point-to-plane normal equations; the caller assembles and solves the vertex system.  Has no
+ * reference counterpart (the reference never moves a vertex).  Needs no engine; errors via ma_last_error(NULL); the scalar arguments are
+ * checked before the first HIP call.  Device arrays, caller-owned workspace.  UNLIKE the other ma_op_*, the call waits for `stream`: the
+ * kernels check the arrays themselves, and a face index outside 0 .. V - 1, a non-finite vertex of a face or a non-finite cloud row is a
+ * returned MA_ERR_INVALID (such a face or point takes no part, so the launch itself stays in bounds).
+ *
+ * ma_op_mesh_fit_pairs: verts (V, 3) fp32 in the CLOUD's units (the caller multiplies by its mesh_scale), faces (M, 3) int32 into them,
+ *   cloud (P, cloud_ld = 6) fp32: xyz, then the normal m, used as given.  All arithmetic is fp32 without FMA contraction, every operation
+ *   rounded on its own in the order csrc/mesh_fit.hpp states, so that a float32 restatement gives the same bits.
+ *   A face is admissible when its indices differ and its inradius |n| / perimeter exceeds `flat` (the rule of ma_op_mesh_udf and
+ *   ma_op_score_meshes, which pass 2^-20), and, with min_cos > 0, for a point whose normal has |nh . m| >= min_cos (nh = the face's unit normal).
+ *   Every point with a non-zero normal is paired with the admissible face that holds the point c nearest to it, the lowest face index on
+ *   equal squared distance, provided |p - c|^2 <= dist * dist:
+ *     pt_face (P) int32    the face, -1 = unpaired
+ *     pt_w (P, 3) fp32     the weights of c on the face's three vertices (0 when unpaired)
+ *     workspace            pt_s (P) fp32 = s = m . (p - c) | pt_r2 (P) fp32 = |p - c|^2 | a status word; each part aligned to 256 bytes
+ *   face_sums (M, MA_MESH_FIT_NSUM) int64, per face over its paired points: [0] their number; then in 2^-32 fixed point (every fp32 term
+ *   converted to double, times 2^32, rounded half to even, summed as int64):
+ *     [1] sum s * s      [2] sum |p - c|^2      [3 + 3 k + a] g[k][a] = sum (w_k * s) * m_a, k = the face's vertex 0..2, a = x, y, z
+ *     [12 + 6 kl + ac] H[kl][ac] = sum (w_k * w_l) * (m_a * m_c), kl in (00, 01, 02, 11, 12, 22), ac in (xx, xy, xz, yy, yz, zz)
+ *   Integer sums: the same bits on every run, for every launch shape and workspace; no floating-point atomics.  With dist <= 1 and unit
+ *   normals every term is at most 1 and the sums stay below 2^55.
+ *   1 <= M <= MA_MESH_FIT_MAX_FACES, 1 <= V <= 3 M, 1 <= P <= MA_MESH_FIT_MAX_POINTS, 0 < dist <= 1, 0 <= min_cos < 1 (0 = no normal test),
+ *   flat >= 0.  workspace: ma_mesh_fit_workspace_bytes(V, M, P) bytes of device memory (0 for arguments outside those limits). */
+#define MA_MESH_FIT_MAX_FACES 4096
+#define MA_MESH_FIT_MAX_POINTS (1 << 22)
+#define MA_MESH_FIT_NSUM 48
+MA_API int    ma_op_mesh_fit_pairs(const float *verts, int V, const int32_t *faces, int M, const float *cloud, int cloud_ld, int P, float dist,
+                                   float min_cos, float flat, int32_t *pt_face, float *pt_w, int64_t *face_sums, void *workspace, size_t ws_bytes,
+                                   void *stream);
+MA_API size_t ma_mesh_fit_workspace_bytes(int V, int M, int P);
+
 /* ---- normals of a raw point cloud, for --input_type pc_xyz (csrc/pc_normals.hpp).  Has no reference counterpart: the reference takes only
  * clouds that already carry unit normals (pc_normal), or meshes.  Needs no engine; errors via ma_last_error(NULL); every argument is
  * checked before the first HIP call.  Device arrays, caller-owned workspace, asynchronous on `stream`.  No atomics: bitwise reproducible.

@@ -90,6 +90,17 @@ refitted to them.  F should span several point spacings and a fraction of the ob
 surviving triples, the agreeing matches and the turn.  Too few matches or agreeing pairs is an error, not a guess.  Out of its reach: a
 solid of large flat faces, whose descriptors all look alike, and a nearly symmetric one, whose half-turn twin overlaps as well as the truth
 -- no overlap check can tell them apart.
+`--fit_iters K` (every input type; 0 = off, the default; 1..32) is the one step AFTER the decoder that moves a vertex: the generated vertices
+lie on the detokenizer's 128-step lattice, up to half a step per axis off the surface, and the 4096 rows the encoder saw know that surface
+far better.  K damped Gauss-Newton steps of the point-to-plane fit pull the merged vertices onto them (`meshanything_amd/mesh_fit.py`): per
+step every row is paired on the GPU with the nearest face within `--fit_dist` (default 4 lattice steps, at most 64; one step is 1/128 of the
+mesh box), optionally only with faces whose normal agrees with the row's to `--fit_normal_cos` (default 0 = off, in [0, 1)), the per-face
+sums of the normal equations come back as exact integers and the host solves the vertex system in float64, each vertex held in place with
+the weight of `--fit_stiffness` points (default 1).  No vertex leaves the ball of `--fit_max_move` (default 2 steps, at most --fit_dist)
+about where the decoder put it, and one without paired rows stays put.  With `--num_candidates` only the chosen mesh is fitted.  The fit is
+kept only if the mean of the two directed distances between mesh and cloud fell, else the decoder's vertices are written: a refusal, not a
+guess; one line per mesh reports the pairs, the RMS before and after, the largest move and which it was.  Faces are not re-merged.  The
+defaults follow from the lattice, not from released weights, which nobody could try offline.
 Multi-GPU: one process per GPU; rank r takes the shapes i % world == r and the weights travel in one RCCL broadcast.
 """
 import argparse
@@ -119,6 +130,14 @@ STEP_FLAGS = (
     ("coarse_radius", {"coarse_points": (1024, lambda v: 64 <= v <= 4096, "in 64..4096"), "coarse_iters": (4096, lambda v: 256 <= v <= 65536, "in 256..65536"),
                        "coarse_dist": (None, lambda v: 0.0 < v < float("inf"), "finite and > 0")}),       # its need of --register_dist: after the table
 )
+
+
+# The mesh fit after the decoder (--fit_iters, 0 = off): the flags that need it, worded like the table above.  Not an input step: it is
+# no part of CloudPrep or Dataset.  Distances are in lattice steps of the decoder.
+FIT_FLAGS = {"fit_dist": (4.0, lambda v: 0.0 < v <= 64.0, "finite, > 0 and at most 64 (lattice steps)"),
+             "fit_max_move": (2.0, lambda v: 0.0 < v < float("inf"), "finite and > 0"),
+             "fit_stiffness": (1.0, lambda v: 0.0 < v < float("inf"), "finite and > 0"),
+             "fit_normal_cos": (0.0, lambda v: 0.0 <= v < 1.0, "in [0, 1) (0 = off)")}
 
 
 def _listed(flags) -> str:
@@ -214,6 +233,17 @@ def get_args(argv=None):
     p.add_argument("--coarse_iters", default=None, type=int, help="with --coarse_radius: pose hypotheses, each from three matches (256..65536, default 4096)")
     p.add_argument("--coarse_dist", default=None, type=float,
                    help="with --coarse_radius: a matched pair agrees with a hypothesis when it lands within this distance (default --coarse_radius / 4)")
+    p.add_argument("--fit_iters", default=0, type=int,
+                   help="fit the generated mesh to the input's 4096 rows on the GPU: this many point-to-plane Gauss-Newton steps on the merged "
+                        "vertices, kept only if the mesh came closer to the cloud (1..32; 0 = off)")
+    p.add_argument("--fit_dist", default=None, type=float,
+                   help="with --fit_iters: pair a row with the nearest face at most this far away, in lattice steps of 1/128 of the mesh box (default 4, at most 64)")
+    p.add_argument("--fit_max_move", default=None, type=float,
+                   help="with --fit_iters: no vertex moves further than this from where the decoder put it, in lattice steps (default 2, at most --fit_dist)")
+    p.add_argument("--fit_stiffness", default=None, type=float,
+                   help="with --fit_iters: every vertex is held in place with the weight of this many paired rows (default 1.0)")
+    p.add_argument("--fit_normal_cos", default=None, type=float,
+                   help="with --fit_iters: pair a row only with faces whose normal agrees with the row's to at least this |cosine| (in [0, 1), default 0 = off)")
     args = p.parse_args(argv)
     for switch, others in STEP_FLAGS:
         flags = [f"--{name}" for name in (switch, *others)]
@@ -229,6 +259,20 @@ def get_args(argv=None):
                 setattr(args, name, default)
             elif ok is not None and not ok(getattr(args, name)):
                 p.error(f"--{name} must be {wording}")
+    if not 0 <= args.fit_iters <= 32:
+        p.error("--fit_iters must be 0 (off) or in 1..32")
+    if args.fit_iters == 0 and any(getattr(args, name) is not None for name in FIT_FLAGS):
+        named = [f"--{name}" for name in FIT_FLAGS if getattr(args, name) is not None]
+        p.error(f"{_listed(named)} need{'s' if len(named) == 1 else ''} --fit_iters > 0")
+    for name, (default, ok, wording) in FIT_FLAGS.items():
+        if args.fit_iters == 0:
+            continue                                     # off: the flags stay None, nothing reads them
+        if getattr(args, name) is None:
+            setattr(args, name, default)
+        elif not ok(getattr(args, name)):
+            p.error(f"--{name} must be {wording}")
+    if args.fit_iters > 0 and args.fit_max_move > args.fit_dist:
+        p.error("--fit_max_move must be at most --fit_dist")
     if args.coarse_radius > 0 and args.register_dist == 0:
         p.error("--coarse_radius needs --register_dist > 0: the coarse pose is where a scan's registration starts")
     if args.align_iters != 0 and not 256 <= args.align_iters <= 65536:
@@ -329,6 +373,10 @@ def main():
             outputs = model(pc, sampling=args.sampling, orient=orient).cpu().numpy()
         for i, d, coords in zip(batch, data, outputs):
             verts, faces = faces_from_coords(coords)
+            if args.fit_iters > 0 and len(faces):        # the merged vertices onto the rows the encoder saw; the faces stay as they are
+                from meshanything_amd.mesh_fit import fit_mesh, report_line
+                verts, fit = fit_mesh(verts, faces, d["pc_normal"], args.fit_iters, args.fit_dist, args.fit_max_move, args.fit_stiffness, args.fit_normal_cos)
+                print(report_line(d["uid"], fit))
             if orient is None:                       # --orient cloud: the winding came with the coordinates
                 faces = fix_normals(verts, faces)
             if split:                                # into the input file's frame, in float64, out of the aligned one if --align_iters turned the part

@@ -143,6 +143,8 @@ SIGNATURES = {
     "ma_score_meshes_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ma_op_mesh_normals": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, C.c_size_t, _P]),
     "ma_mesh_normals_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "ma_op_mesh_fit_pairs": (_I, [_P, _I, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ma_mesh_fit_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ma_op_pc_knn": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "ma_pc_knn_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "ma_op_pc_normals": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),

@@ -40,6 +40,7 @@
 #include "surface_sample.hpp"
 #include "watertight.hpp"
 #include "mesh_normals.hpp"
+#include "mesh_fit.hpp"
 #include "mesh_score.hpp"
 #include "pc_normals.hpp"
 #include "pc_fps.hpp"
@@ -1082,6 +1083,36 @@ int ma_op_mesh_normals(const float* coords, int B, int F, const float* cloud, in
         if (ws_bytes < mnorm::normals_ws_bytes(B, F)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_normals: workspace smaller than ma_mesh_normals_workspace_bytes(B, F)");
         HIP_CHECK(mnorm::launch_mesh_normals(coords, B, F, cloud, cloud_ld, P, n_per_cloud, mesh_scale, face_agree, nscores, workspace,
                                              reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- fit of a generated mesh to its cloud: pairing and per-face sums (csrc/mesh_fit.hpp) ----------------------------------------
+static bool mesh_fit_shape_ok(int V, int M, int P) {
+    return M >= 1 && M <= MA_MESH_FIT_MAX_FACES && V >= 1 && V <= 3 * M && P >= 1 && P <= MA_MESH_FIT_MAX_POINTS;
+}
+
+size_t ma_mesh_fit_workspace_bytes(int V, int M, int P) { return mesh_fit_shape_ok(V, M, P) ? fit::fit_ws_bytes(P) : 0; }
+
+int ma_op_mesh_fit_pairs(const float* verts, int V, const int32_t* faces, int M, const float* cloud, int cloud_ld, int P, float dist, float min_cos, float flat,
+                         int32_t* pt_face, float* pt_w, int64_t* face_sums, void* workspace, size_t ws_bytes, void* stream) {
+    return guarded(nullptr, [&] {
+        if (!mesh_fit_shape_ok(V, M, P)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: need 1 <= M <= 4096, 1 <= V <= 3 M and 1 <= P <= 2^22");
+        if (!verts || !faces || !cloud || !pt_face || !pt_w || !face_sums || !workspace) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: null pointer");
+        if (cloud_ld != 6) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: cloud_ld must be 6 (xyz and the normal)");
+        if (!std::isfinite(dist) || !(dist > 0.f) || dist > 1.0f) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: dist must be finite, > 0 and at most 1");
+        if (!(min_cos >= 0.f && min_cos < 1.0f)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: min_cos must be in [0, 1)");
+        if (!std::isfinite(flat) || !(flat >= 0.f)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: flat must be finite and >= 0");
+        if (ws_bytes < fit::fit_ws_bytes(P)) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: workspace smaller than ma_mesh_fit_workspace_bytes(V, M, P)");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        HIP_CHECK(fit::launch_mesh_fit_pairs(verts, V, faces, M, cloud, cloud_ld, P, dist, min_cos, flat, pt_face, pt_w, face_sums, workspace, s));
+        fit::FitWs ws;
+        fit::fit_ws_bytes(P, &ws, workspace);
+        int status = 0;                                              // what the kernels found in the arrays themselves
+        HIP_CHECK(hipMemcpyAsync(&status, ws.status, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (status & fit::ST_FACE_INDEX) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: a face index is outside 0 .. V - 1");
+        if (status & fit::ST_VERT_NONFINITE) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: a vertex of a face has a non-finite coordinate");
+        if (status & fit::ST_CLOUD_NONFINITE) throw MaError(MA_ERR_INVALID, "ma_op_mesh_fit_pairs: the cloud has a non-finite coordinate or normal");
     });
 }
 
